@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — env steps/sec of the batched Stack-v0 hot path (BASELINE.json metric) + the DQN rollout/update leg.
 
-  python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4]
+  python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps of the headline workload and prints the line.  `--full` adds everything
+else below (leg B beside leg A, both rollout precisions, the CPU baseline and reward parity, the 54-step and free-running
+windows, the solver statistics of an extra episode).  `--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy in float32 (see `dump_env_outputs`, `dump_dqn_outputs`); with the same arguments the inputs are the same.
 
 Launch.  `--gpus N` with N > 1 starts N fresh child processes itself (one per GPU, rendezvous on 127.0.0.1; the
 parent never touches the GPU and never execs); under `python -m torch.distributed.run` (RANK / WORLD_SIZE already in
@@ -22,9 +27,9 @@ Workloads (BASELINE.json `configs`):
          labelled entry, bf16.  `--config 2|3|4` makes that leg the headline `value` instead.
 
 Extra objects on the JSON line: `roofline` (render kernel K2, HBM-bound: algorithmic bytes / HIP-event time measured in
-the timed region), `settle` (K1 launch statistics), `cpu_baseline` (the CPU oracle timed on this
-host's cores on a bounded sample of leg A's workload), `reward_mse_vs_cpu`, `dqn` (leg B incl. its own `roofline` with
-bound "mfma").
+the timed region), `settle` (K1 launch statistics), and with --full `cpu_baseline` (the CPU oracle
+timed on this host's cores on a bounded sample of leg A's workload), `reward_mse_vs_cpu`, `dqn` (leg B incl. its own
+`roofline` with bound "mfma").
 """
 import argparse
 import json
@@ -83,6 +88,11 @@ def parse_args(argv=None):
                   help='N > 1: seconds leg B (DQN) may take after leg A before the launcher ends the ranks and prints leg A')
   ap.add_argument('--launch-only', action='store_true',
                   help='rehearsal without a GPU: spawn, rendezvous, barriers and aggregation only; value is null')
+  ap.add_argument('--full', action='store_true',
+                  help='also run everything beside the headline: leg B and both rollout precisions, the CPU legs, the 54-step '
+                       'and free-running windows, solver statistics (a plain run times the headline only)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last one returned as DIR/<name>.npy (float32; rank 0)')
   return ap.parse_args(argv)
 
 
@@ -261,6 +271,40 @@ def cpu_baseline(L, seed, kw, budget_envs=48, episodes=20):
   }
 
 
+DUMP_BYTES = 48 << 20     # --dump-outputs: at most this many bytes in all; beyond it a fixed sample of the envs
+
+
+def _save_float32(dir_, arrays):
+  import numpy as np
+  os.makedirs(dir_, exist_ok=True)
+  for name, a in arrays.items():
+    np.save(os.path.join(dir_, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def dump_env_outputs(dir_, step_out):
+  """Leg A's last timed `env.step` as float32: obs_map [k, H, W, 2], obs_obj [k, h, w, 1], reward [k] (or [k, keys]) and
+  done [k] of k envs — all of them when that fits DUMP_BYTES, else a fixed sample (numpy seed 0, in index order)."""
+  import numpy as np
+  import torch
+  (om, oo), reward, done = step_out
+  B = om.shape[0]
+  per_env = 4 * (om[0].numel() + oo[0].numel() + reward[0].numel() + 1)
+  k = min(B, DUMP_BYTES // per_env)
+  idx = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+  idx = torch.from_numpy(idx).to(om.device)
+  _save_float32(dir_, {name: t.index_select(0, idx).float().cpu().numpy()
+                       for name, t in (('obs_map', om), ('obs_obj', oo), ('reward', reward), ('done', done))})
+
+
+def dump_dqn_outputs(dir_, net):
+  """Leg B as the headline (--config 2|3|4): the Q-net's parameters after the last timed update, flattened in
+  `net.parameters()` order, as float32."""
+  import torch
+  with torch.no_grad():
+    flat = torch.cat([p.detach().float().reshape(-1) for p in net.parameters()])
+  _save_float32(dir_, {'q_params': flat.cpu().numpy()})
+
+
 def build_info():
   from stackrl_amd import build as _b
   i = _b.info(_b.LIB) or {}
@@ -384,9 +428,16 @@ def env_leg(args, rank, world, pool, barrier, solver_kw):
     alg += B * alg_bytes_per_env(res, r, nb)
   barrier()
   dt = time.perf_counter() - t0
-  last()     # raises if any env diverged / action invalid
+  last_out = last()     # raises if any env diverged / action invalid
   ms, nl = env.kernel_times()
   env.set_profiling(False)
+  if args.dump_outputs and rank == 0 and args.config == 1:      # leg A is the headline
+    dump_env_outputs(args.dump_outputs, last_out)
+  out = dict(B=B, L=L, res=res, r=r, dt=dt, placed=placed, alg=alg, rocks=rocks, ms=ms, nl=nl, config=env.config)
+  if not args.full:
+    env.close()
+    torch.cuda.synchronize()
+    return out
   # the same loop over a window of 54 calls (six whole episodes: every fill level of the scene weighs the same), reported
   # beside the contract's K-step figure as value_long
   long_steps, long_value = 54, None
@@ -452,9 +503,7 @@ def env_leg(args, rank, world, pool, barrier, solver_kw):
     subs.append(env.state()[2].sum(1))
     sweeps.append(env.sweeps())
   do_step()[0]()
-  sub, sw = np.stack(subs), np.stack(sweeps)
-  out = dict(B=B, L=L, res=res, r=r, dt=dt, placed=placed, alg=alg, rocks=rocks, ms=ms, nl=nl, sub=sub, sw=sw, config=env.config,
-             long_value=long_value, long_steps=long_steps, free_run=free_run)
+  out.update(sub=np.stack(subs), sw=np.stack(sweeps), long_value=long_value, long_steps=long_steps, free_run=free_run)
   env.close()
   torch.cuda.synchronize()
   return out
@@ -514,10 +563,10 @@ def rccl_group(args, world):
   return _RCCL['pg']
 
 
-def dqn_leg(args, rank, world, pool, barrier, solver_kw, dtype):
+def dqn_leg(args, rank, world, pool, barrier, solver_kw, dtype, dump=False):
   """`Training.run` (training.py:338-380) for --dqn-iters iterations after --dqn-warmup: per iteration one rollout forward
   over the rank's envs (`agent.collect`), one non-blocking vectorised env step on a side stream, one minibatch-32 update
-  (`agent.train`, with the gradient all-reduce when world > 1)."""
+  (`agent.train`, with the gradient all-reduce when world > 1).  `dump`: this leg is the headline; --dump-outputs applies."""
   import torch
   import torch.distributed as dist
   from stackrl_amd import env as envs, nets, qops
@@ -620,6 +669,8 @@ def dqn_leg(args, rank, world, pool, barrier, solver_kw, dtype):
   barrier()
   dt = time.perf_counter() - t0
   agent.policy_timer = None
+  if dump and args.dump_outputs and rank == 0:
+    dump_dqn_outputs(args.dump_outputs, net)
   fwd_ms = sum(a.elapsed_time(b) for a, b in ptimer.pairs) / len(ev)
   upd_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / len(ev)
   # all-reduce of the gradient bucket, timed on its own after the loop (inside the update it hides in upd_ms)
@@ -716,7 +767,7 @@ def worker(args):
   pool = assets.default_pool()           # synthetic rocks, generator seed 11 (cached)
 
   cpu = None
-  if rank == 0 and args.gpus == 1 and not args.no_cpu:      # the CPU legs belong to the N = 1 run
+  if args.full and rank == 0 and args.gpus == 1 and not args.no_cpu:      # the CPU legs belong to the N = 1 run
     from oracle import oracle as _o
     _o.build()
     cpu = cpu_baseline(L, args.seed, solver_kw)     # before any GPU initialisation in this process
@@ -744,7 +795,7 @@ def worker(args):
   dt_max, placed_all = aggregate(a['dt'], a['placed'], world, 'cpu')
 
   def make_line(dqn, mse):
-    B, res, ms, nl, sub, sw = a['B'], a['res'], a['ms'], a['nl'], a['sub'], a['sw']
+    B, res, ms, nl = a['B'], a['res'], a['ms'], a['nl']
     traffic, traffic_source = traffic_record(B, a['L'], res, a['alg'] / max(int(nl[1]), 1))
     render_s = float(ms[1]) / 1e3
     cfg = a['config']
@@ -761,11 +812,7 @@ def worker(args):
         'parallelism': 'env-shard x{}'.format(args.gpus),
         'mesh_pool': '{} synthetic rocks (generator seed 11)'.format(len(pool)),
       },
-      'step_calls_per_s': args.steps * B * args.gpus / dt_max,
-      # the same loop over 54 calls = six whole episodes (the K-step window above starts mid-episode and weighs the fuller scenes more)
-      'value_long': None if a.get('long_value') is None else {'value': a['long_value'], 'steps': a['long_steps'], 'unit': 'env_steps/s'},
-      # the same envs as handles that are not kept in lock-step (see env_leg): a capability of the interface, not the contract's figure
-      'value_free_running': a.get('free_run'),
+      'step_calls_per_s': args.steps * B * args.gpus / dt_max, 'full': args.full,
       # which build of the env library was timed (stackrl_amd/build.py: 'vectorised+rewritten' = SLP vectoriser + the pass of
       # isa_fix.py over the assembly; 'safe' = the fall-back without the vectoriser) and the hash of the sources it carries
       'env_library': build_info(),
@@ -788,15 +835,25 @@ def worker(args):
       },
       'settle': {
         'kernel': 'srl_k_step', 'avg_launch_ms': float(ms[0]) / max(int(nl[0]), 1), 'launches': int(nl[0]),
-        'share_of_wall': float(ms[0]) / 1e3 / a['dt'], 'substeps_mean': float(sub.mean()),
-        'substeps_mean_of_per_step_max': float(sub.max(1).mean()), 'substeps_max': int(sub.max()),
-        'sweeps_per_substep_mean': float(sw.sum() / max(sub.sum(), 1)),
-        'sweeps_mean': float(sw.mean()), 'sweeps_mean_of_per_step_max': float(sw.max(1).mean()),
+        'share_of_wall': float(ms[0]) / 1e3 / a['dt'],
         'note': 'latency-bound: one launch lasts as long as its slowest env (stop criterion simulator.py:322-335)',
         **settle_counters(B, a['L'], res),
       },
-      'cpu_baseline': cpu, 'reward_mse_vs_cpu': mse, 'dqn': dqn,
     }
+    if args.full:
+      sub, sw = a['sub'], a['sw']
+      line['settle'].update(
+        substeps_mean=float(sub.mean()), substeps_mean_of_per_step_max=float(sub.max(1).mean()), substeps_max=int(sub.max()),
+        sweeps_per_substep_mean=float(sw.sum() / max(sub.sum(), 1)),
+        sweeps_mean=float(sw.mean()), sweeps_mean_of_per_step_max=float(sw.max(1).mean()))
+      line.update({
+        # the same loop over 54 calls = six whole episodes (the K-step window above starts mid-episode and weighs the fuller scenes more)
+        'value_long': None if a.get('long_value') is None else {'value': a['long_value'], 'steps': a['long_steps'], 'unit': 'env_steps/s'},
+        # the same envs as handles that are not kept in lock-step (see env_leg): a capability of the interface, not the contract's figure
+        'value_free_running': a.get('free_run'),
+        'cpu_baseline': cpu, 'reward_mse_vs_cpu': mse})
+    if args.full or dqn is not None:
+      line['dqn'] = dqn
     if args.config != 1 and dqn:
       # the DQN leg as the headline: the fp32-class rollout (bf16x3 products; the reference computes in fp32) when it was run
       d = dqn.get('bf16x3') or next(iter(dqn.values()))
@@ -806,19 +863,21 @@ def worker(args):
       line['config'] = dict(line['config'], workload=d['workload'], note='leg A (config keys above) is reported under env_only')
     return line
 
-  if rank == 0 and world > 1 and os.environ.get('SRL_BENCH_CHILD') == '1' and args.config == 1 and not args.no_dqn:
+  if rank == 0 and world > 1 and os.environ.get('SRL_BENCH_CHILD') == '1' and args.config == 1 and args.full and not args.no_dqn:
     # leg A is complete on every rank: hand the headline to the launcher now, so that a rank lost in leg B (whose
     # collectives the others would then wait in) cannot take it down; the final line below replaces it
     emit(make_line({'error': 'a rank ended during leg B (DQN); leg A above is complete'}, None), provisional=True)
 
   dqn = None
-  if not args.no_dqn:
+  if (args.config != 1 or args.full) and not args.no_dqn:
     dqn = {}
-    for dtype in (['bf16x3', 'bf16'] if args.rollout == 'both' else ['bf16x3' if args.rollout == 'f32' else args.rollout]):
+    dtypes = ['bf16x3', 'bf16'] if args.rollout == 'both' else ['bf16x3' if args.rollout == 'f32' else args.rollout]
+    headline = dtypes[0]          # the fp32-class rollout when it is run (the reference computes in fp32)
+    for dtype in (dtypes if args.full else [headline]):
       # leg B must not take the headline down with it: an exception is recorded, not raised (with the DQN leg as the
       # headline, --config 2|3|4, it is raised)
       try:
-        dqn[dtype] = dqn_leg(args, rank, world, pool, barrier, solver_kw, dtype)
+        dqn[dtype] = dqn_leg(args, rank, world, pool, barrier, solver_kw, dtype, dump=args.config != 1 and dtype == headline)
       except Exception as e:   # noqa: BLE001
         if args.config != 1 or world > 1:   # with other ranks waiting in this leg's collectives there is no going on
           raise
@@ -828,7 +887,7 @@ def worker(args):
         torch.cuda.synchronize()
 
   mse = None
-  if rank == 0 and args.gpus == 1 and not args.no_cpu:
+  if args.full and rank == 0 and args.gpus == 1 and not args.no_cpu:
     mse = reward_mse(args, pool, L, solver_kw)
 
   if rank == 0:

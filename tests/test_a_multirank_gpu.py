@@ -67,7 +67,7 @@ def _run_bench(extra_env, *flags):
   env.pop('RANK', None); env.pop('WORLD_SIZE', None)
   p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--same-device', '--backend', 'gloo',
                       '--no-cpu', '--envs', '64', '--steps', '3', '--warmup', '1', '--dqn-envs', '32', '--dqn-rocks', '4',
-                      '--dqn-iters', '3', '--dqn-warmup', '1', '--dqn-slots', '8'] + list(flags),
+                      '--dqn-iters', '3', '--dqn-warmup', '1', '--dqn-slots', '8', '--full'] + list(flags),
                      env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
   lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
   return p.returncode, lines, p.stderr.decode()

@@ -308,6 +308,29 @@ def test_bench_aggregation_world_size_2_gloo(tmp_path):
   assert res == {'dt': 2.0, 'placed': 300.0}
 
 
+def test_bench_dump_outputs_float32_capped_fixed_sample(tmp_path, monkeypatch):
+  """bench.py --dump-outputs: the last step's arrays as float32 .npy, every env while they fit the byte cap, else the same
+  seeded sample of envs (in index order) on every run."""
+  import bench
+  B, H, h = 10, 8, 4
+  om = torch.randint(0, 256, (B, H, H, 2), dtype=torch.uint8)
+  oo = torch.randint(0, 256, (B, h, h, 1), dtype=torch.uint8)
+  rw, dn = torch.randn(B), torch.rand(B) < 0.5
+  bench.dump_env_outputs(str(tmp_path / 'all'), ((om, oo), rw, dn))
+  got = {n: np.load(str(tmp_path / 'all' / (n + '.npy'))) for n in ('obs_map', 'obs_obj', 'reward', 'done')}
+  assert all(a.dtype == np.float32 for a in got.values())
+  assert np.array_equal(got['obs_map'], om.numpy()) and np.array_equal(got['obs_obj'], oo.numpy())
+  assert np.array_equal(got['reward'], rw.numpy()) and np.array_equal(got['done'], dn.numpy())
+  per_env = 4 * (H * H * 2 + h * h + 2)
+  monkeypatch.setattr(bench, 'DUMP_BYTES', 3 * per_env + 1)
+  for d in ('s1', 's2'):
+    bench.dump_env_outputs(str(tmp_path / d), ((om, oo), rw, dn))
+  s1, s2 = (np.load(str(tmp_path / d / 'obs_map.npy')) for d in ('s1', 's2'))
+  assert s1.shape == (3, H, H, 2) and np.array_equal(s1, s2)
+  idx = [i for i in range(B) if any(np.array_equal(om[i].numpy(), s) for s in s1)]
+  assert len(idx) == 3 and np.array_equal(np.stack([om[i].numpy() for i in idx]), s1)
+
+
 # ---------------------------------------------------------------------------- training loop, logs, checkpoints
 class _ToyEnv(object):
   """The env interface `Training` uses (training.py:105, :267-275, :335-368) on CPU tensors: episodes of `L` steps,

@@ -13,28 +13,28 @@ SECTIONS="${@:-env qnet configs}"
 for S in $SECTIONS; do
 case $S in
 env)
-  python bench.py > $O/bench_final.json 2> $O/bench_final.err || exit 1
+  python bench.py --full > $O/bench_final.json 2> $O/bench_final.err || exit 1
   echo bench done
-  python bench.py --steps 20 --warmup 5 --no-dqn > $O/bench_driver_window.json 2> $O/bench_driver_window.err || exit 1
+  python bench.py --full --steps 20 --warmup 5 --no-dqn > $O/bench_driver_window.json 2> $O/bench_driver_window.err || exit 1
   export SRL_NO_FREE_RUN=1
   rm -rf $O/prof $O/pmc_f $O/pmc_w $O/pmc_s1 $O/pmc_s2
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --no-cpu --no-dqn --steps 20 --warmup 5 > $O/prof.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --no-cpu --no-dqn --steps 20 --warmup 5 > $O/prof.log 2>&1 || exit 1
   python tools/kernel_stats.py $O/prof --prefix srl_k > $O/bench_kernel_stats.csv || exit 1
   cp $(find $O/prof -name '*kernel_stats.csv' | head -1) $O/bench_kernel_stats_rocprofv3.csv
   echo stats done
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -- python3 bench.py --no-cpu --no-dqn --steps 20 --warmup 5 > $O/pmc_f.log 2>&1 || exit 1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -- python3 bench.py --no-cpu --no-dqn --steps 20 --warmup 5 > $O/pmc_w.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -- python3 bench.py --full --no-cpu --no-dqn --steps 20 --warmup 5 > $O/pmc_f.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -- python3 bench.py --full --no-cpu --no-dqn --steps 20 --warmup 5 > $O/pmc_w.log 2>&1 || exit 1
   python tools/pmc_summary.py $O/pmc_f $O/pmc_w srl_k_render 111656960 --wgs 1024 > $O/render_pmc.json || exit 1
   echo render pmc done
-  rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $O/pmc_s1 -- python3 bench.py --no-cpu --no-dqn --steps 20 --warmup 5 > $O/pmc_s1.log 2>&1 || exit 1
-  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/pmc_s2 -- python3 bench.py --no-cpu --no-dqn --steps 20 --warmup 5 > $O/pmc_s2.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $O/pmc_s1 -- python3 bench.py --full --no-cpu --no-dqn --steps 20 --warmup 5 > $O/pmc_s1.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/pmc_s2 -- python3 bench.py --full --no-cpu --no-dqn --steps 20 --warmup 5 > $O/pmc_s2.log 2>&1 || exit 1
   python tools/pmc_insts.py srl_k_step $O/pmc_s1 $O/pmc_s2 --wgs 1024 --json $O/settle_pmc.json > $O/settle_pmc.txt || exit 1
   echo settle pmc done
   # the settle kernel at a batch-bound shape (configs[2]'s 4,096 envs x 16 rocks: the two-wave variant srl_k_step_t128, ordered
   # launch): the same counters
   rm -rf $O/pmc_b1 $O/pmc_b2
-  rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $O/pmc_b1 -- python3 bench.py --no-cpu --no-dqn --envs 4096 --rocks 16 --steps 17 --warmup 4 > $O/pmc_b1.log 2>&1 || exit 1
-  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/pmc_b2 -- python3 bench.py --no-cpu --no-dqn --envs 4096 --rocks 16 --steps 17 --warmup 4 > $O/pmc_b2.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $O/pmc_b1 -- python3 bench.py --full --no-cpu --no-dqn --envs 4096 --rocks 16 --steps 17 --warmup 4 > $O/pmc_b1.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/pmc_b2 -- python3 bench.py --full --no-cpu --no-dqn --envs 4096 --rocks 16 --steps 17 --warmup 4 > $O/pmc_b2.log 2>&1 || exit 1
   python tools/pmc_insts.py srl_k_step_t128 $O/pmc_b1 $O/pmc_b2 --wgs 4096 --json $O/settle_pmc_4096x16.json > $O/settle_pmc_4096x16.txt || exit 1
   unset SRL_NO_FREE_RUN
   python tools/argmax_precision.py 4608 1 > $O/rollout_argmax.json 2> $O/rollout_argmax.err
@@ -54,9 +54,9 @@ qnet)
   ;;
 configs)
   python tools/bench_shapes.py > $O/env_shapes.txt 2>&1
-  python bench.py --config 2 --no-cpu --steps 17 --warmup 4 > $O/bench_config2.json 2> $O/bench_config2.err || exit 1
-  python bench.py --config 3 --no-cpu --steps 17 --warmup 4 > $O/bench_config3.json 2> $O/bench_config3.err || exit 1
-  python bench.py --config 4 --no-cpu --steps 33 --warmup 4 > $O/bench_config4.json 2> $O/bench_config4.err || exit 1
+  python bench.py --full --config 2 --no-cpu --steps 17 --warmup 4 > $O/bench_config2.json 2> $O/bench_config2.err || exit 1
+  python bench.py --full --config 3 --no-cpu --steps 17 --warmup 4 > $O/bench_config3.json 2> $O/bench_config3.err || exit 1
+  python bench.py --full --config 4 --no-cpu --steps 33 --warmup 4 > $O/bench_config4.json 2> $O/bench_config4.err || exit 1
   ;;
 esac
 done
