@@ -131,6 +131,12 @@ int srl_set_profiling(srl_env* env, int32_t enable);
  * handle's own n_envs, says which one fits.  Results do not depend on it (the parity tests run both builds). */
 int srl_set_concurrent_envs(srl_env* env, int32_t n_envs_on_device);
 
+/* Test hook, after srl_load_meshes (which chooses it): the settle kernel variant this handle launches.  threads = threads
+ * per env workgroup, points_per_thread = pair-manifold points per thread, kernel = 0: srl_k_step, up to 8 rocks; 1:
+ * srl_k_step_pp1, 9 - 16 rocks, four waves; 2: srl_k_step_pp2, 17 - 32 rocks; 3: srl_k_step_t128, 9 - 16 rocks, two waves.
+ * Any output may be null. */
+int srl_get_step_variant(srl_env* env, int32_t* threads, int32_t* points_per_thread, int32_t* kernel);
+
 /* Launch order of the settle kernel's workgroups (one per env).  The reference's `ParallelEnv` collects its worker
  * processes' results as they come (utils.py:540-543) and a vectorised step lasts as long as its slowest env (the stop
  * criterion of simulator.py:322-335); a batch that outnumbers the workgroups the device holds at once therefore starts the

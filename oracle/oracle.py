@@ -120,6 +120,13 @@ class OracleEnv(object):
     v = None if velocities is None else np.ascontiguousarray(velocities, np.float32)
     self.L.srlo_set_body_state(self.h, _p(p), _p(v))
 
+  def debug_slots(self, i):
+    """Manifold-slot statistics of env i (`srlo_debug_slots`): (active slots, slots with contact points, contact points,
+    colours)."""
+    out = np.zeros(4, np.int32)
+    self.L.srlo_debug_slots(self.h, ctypes.c_int32(int(i)), _p(out))
+    return tuple(int(x) for x in out)
+
   def step_simulation(self, n=1):
     self.L.srlo_step_simulation(self.h, ctypes.c_int32(int(n)))
 

@@ -518,6 +518,15 @@ int srl_set_concurrent_envs(srl_env* env, int32_t n_envs_on_device) {
   return SRL_OK;
 }
 
+int srl_get_step_variant(srl_env* env, int32_t* threads, int32_t* points_per_thread, int32_t* kernel) {
+  if (!env) return fail(SRL_EINVAL, "null env");
+  if (!env->d_mh) return fail(SRL_ENOMESH, "srl_load_meshes must be called first (it chooses the variant)");
+  if (threads) *threads = env->step_threads;
+  if (points_per_thread) *points_per_thread = env->step_pp == 2 || env->step_pp == 3 ? 2 : 1;
+  if (kernel) *kernel = env->step_pp;
+  return SRL_OK;
+}
+
 int srl_set_launch_order(srl_env* env, int32_t mode) {
   if (!env) return fail(SRL_EINVAL, "null env");
   if (mode < -1 || mode > 1) return fail(SRL_EINVAL, "launch order mode must be -1 (by batch size), 0 (index order) or 1 (highest release first)");

@@ -250,6 +250,13 @@ class VecStackEnv(object):
     _check(self._lib.srl_get_state(self._h, _np_ptr(poses), _np_ptr(nb), _np_ptr(sub), _np_ptr(st)))
     return poses, nb, sub, st
 
+  def step_variant(self):
+    """Test hook (`srl_get_step_variant`): (threads per env workgroup, pair points per thread, kernel) of the settle kernel
+    this handle launches; kernel 0 = srl_k_step, 1 = srl_k_step_pp1, 2 = srl_k_step_pp2, 3 = srl_k_step_t128."""
+    t, pp, k = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _check(self._lib.srl_get_step_variant(self._h, ctypes.byref(t), ctypes.byref(pp), ctypes.byref(k)))
+    return t.value, pp.value, k.value
+
   def velocities(self):
     v = np.zeros((self._B, _config.MAX_BODIES, 8), np.float32)
     _check(self._lib.srl_get_velocities(self._h, _np_ptr(v)))

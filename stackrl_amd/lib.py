@@ -35,6 +35,7 @@ _SIGS = {
   'srl_get_order_kernel_times': (ctypes.c_int, [_VP, _VP, _VP]),
   'srl_get_launch_order': (ctypes.c_int, [_VP, _VP, _VP]),
   'srl_set_concurrent_envs': (ctypes.c_int, [_VP, ctypes.c_int32]),
+  'srl_get_step_variant': (ctypes.c_int, [_VP, _VP, _VP, _VP]),
   'srl_set_launch_order': (ctypes.c_int, [_VP, ctypes.c_int32]),
   'srl_build_info': (ctypes.c_char_p, []),
   'srl_get_stage_records': (ctypes.c_int, [_VP, _VP, ctypes.c_int64]),

@@ -12,6 +12,7 @@ source is clean); the Q-net library is built without the vectoriser.  These test
 the way stackrl_amd/build.py does AND take the shipped .so files apart (no GPU needed), so that a later flag, compiler or
 source change — or a stale library — cannot bring the form back unnoticed."""
 import os
+import re
 from concurrent.futures import ThreadPoolExecutor
 
 from stackrl_amd import build, isa_fix
@@ -62,10 +63,15 @@ def test_the_vectoriser_does_emit_the_form_and_the_pass_removes_all_of_it():
   assert len(isa_fix.flagged(raw)) > 100          # (955 with the compiler of this image)
   text, n, left = isa_fix.rewrite(raw)
   assert n == len(isa_fix.flagged(raw)) and left == 0 and not isa_fix.flagged(text)
-  # nothing but the flagged lines changes
-  assert sum(a != b for a, b in zip(raw.split('\n'), isa_fix.rewrite(raw)[0].split('\n'))) >= 0
-  changed = [(a, b) for a, b in zip(raw.split('\n'), [isa_fix._fix(l)[0] for l in raw.split('\n')]) if a != b]
+  # nothing but the flagged lines changes, and the rewritten text is the per-line fixes in their places and order
+  fixed = [isa_fix._fix(l)[0] for l in raw.split('\n')]
+  assert text == '\n'.join(fixed)
+  changed = [(a, b) for a, b in zip(raw.split('\n'), fixed) if a != b]
   assert len(changed) == n and all(isa_fix.BAD.match(a) for a, _ in changed)
+  # a split adds one line (two with the crosswise swap); a swap adds none
+  added = sum(b.count('\n') for _, b in changed)
+  assert len(text.split('\n')) == len(raw.split('\n')) + added
+  assert added == sum(1 + ('v_swap_b32' in b) for _, b in changed if '\n' in b)
 
 
 def test_the_rewrite_swaps_sources_and_modifier_bits():
@@ -99,3 +105,133 @@ def test_the_rewrite_swaps_sources_and_modifier_bits():
                 '\tv_pk_add_f32 v[50:51], v[52:53], v[50:51] neg_lo:[0,1] neg_hi:[0,1]',
                 '\tv_add_f32_e32 v1, v2, v3'):
     assert f(clean) == (clean, False) and not isa_fix.BAD.match(clean)
+
+
+# ------------------------------------------------------------------------------------------------ LDS read windows
+# The settle kernels issue `ds_read_b128` from inline asm (settle.hip cg_request / cg_request_first) into "=&v" outputs
+# that hold the data only from the hand-written `s_waitcnt lgkmcnt(k)` of cg_arrive on: the compiler takes the registers
+# as written when the asm statement ends.  A copy or spill of those registers in between would read them before the data
+# arrives.  So, in the disassembly of the shipped settle kernels, every `ds_read_b128` has a window that runs up to the first
+# wait that retires it — `lgkmcnt(k)` with k <= the LDS operations issued after the read (LDS operations return in order;
+# scalar loads do not, and count as none here, which can only lengthen a window) — and in it no instruction names one of
+# the read's destination registers, and no branch leaves or enters it (DESIGN: every read is waited for in the block that
+# issued it).
+SETTLE_KERNELS = ('srl_k_step', 'srl_k_step_pp1', 'srl_k_step_pp2', 'srl_k_step_t128')
+_FUNC = re.compile(r'^([0-9a-f]+) <([^>]+)>:$')
+_LINE = re.compile(r'^\s+([a-z_0-9]+)\b([^/]*)(?://\s*([0-9A-Fa-f]+):[^<]*(?:<([^>+]+)\+0x([0-9a-f]+)>)?)?')
+_VREG = re.compile(r'(?<![\w\[])v(\d+)\b|(?<![\w\[])v\[(\d+):(\d+)\]')
+_LGKM = re.compile(r'lgkmcnt\((\d+)\)')
+_BRANCH = ('s_branch', 's_cbranch_', 's_setpc_', 's_swappc_', 's_endpgm', 's_call_')
+
+
+def _vregs(operands):
+  out = set()
+  for m in _VREG.finditer(operands):
+    if m.group(1) is not None:
+      out.add(int(m.group(1)))
+    else:
+      out.update(range(int(m.group(2)), int(m.group(3)) + 1))
+  return out
+
+
+def _functions(text):
+  """{name: [(address, mnemonic, operands, branch target address or None)]} of an `llvm-objdump -d` text."""
+  funcs, cur, base = {}, None, 0
+  for line in text.splitlines():
+    m = _FUNC.match(line)
+    if m:
+      base, cur = int(m.group(1), 16), m.group(2)
+      funcs[cur] = []
+      continue
+    m = _LINE.match(line)
+    if cur is None or not m or m.group(3) is None:
+      continue
+    target = None
+    if m.group(4) is not None:
+      target = base + int(m.group(5), 16) if m.group(4) == cur else -1
+    funcs[cur].append((int(m.group(3), 16), m.group(1), m.group(2).strip(), target))
+  return funcs
+
+
+def lds_window_violations(insns):
+  """[(read address, problem)] of the `ds_read_b128` windows of one function's instruction list."""
+  targets = {t for _, _, _, t in insns if t is not None}
+  bad = []
+  for i, (addr, op, opnds, _) in enumerate(insns):
+    if op != 'ds_read_b128':
+      continue
+    dst = _vregs(opnds.split(',')[0])
+    later_ds, closed = 0, False
+    for addr2, op2, opnds2, _ in insns[i + 1:]:
+      if op2 == 's_waitcnt':
+        k = _LGKM.search(opnds2)
+        if k and int(k.group(1)) <= later_ds:
+          closed = True
+          break
+        continue
+      if addr2 in targets:
+        bad.append((addr, 'branch target {:#x} inside the window'.format(addr2)))
+        break
+      if op2.startswith(_BRANCH):
+        bad.append((addr, '{} at {:#x} inside the window'.format(op2, addr2)))
+        break
+      if dst & _vregs(opnds2):
+        bad.append((addr, '{} {} at {:#x} names a destination register before the wait'.format(op2, opnds2, addr2)))
+        break
+      if op2.startswith('ds_'):
+        later_ds += 1
+    else:
+      if not closed:
+        bad.append((addr, 'never waited for'))
+  return bad
+
+
+def settle_window_report(text):
+  """{kernel: (ds_read_b128 count, violations)} of the settle kernels of one disassembly."""
+  funcs = _functions(text)
+  return {k: (sum(op == 'ds_read_b128' for _, op, _, _ in funcs[k]), lds_window_violations(funcs[k]))
+          for k in SETTLE_KERNELS if k in funcs}
+
+
+def test_lds_reads_of_the_settle_kernels_are_not_touched_before_their_wait():
+  from stackrl_amd import build
+  build.build()
+  texts = isa_fix.shipped_asm(build.LIB)
+  report = {}
+  for t in texts:
+    report.update(settle_window_report(t))
+  assert sorted(report) == sorted(SETTLE_KERNELS)
+  # the scan saw the hand-issued reads: the 128-thread variant requests a ground point's record ahead (seven reads a record)
+  assert report['srl_k_step'][0] >= 28 and all(n > 0 for n, _ in report.values())
+  for k, (n, bad) in report.items():
+    assert not bad, '{}: {} of {} ds_read_b128 windows broken: {}'.format(k, len(bad), n, ['{:#x}: {}'.format(a, w) for a, w in bad[:5]])
+
+
+_SYNTH = """0000000000001000 <srl_k_step>:
+\tds_read_b128 v[10:13], v2 offset:16                         // 000000001000: D9FE0010 0A000002
+\tds_read_b128 v[14:17], v2 offset:32                         // 000000001008: D9FE0020 0E000002
+\tv_add_f32_e32 v20, v21, v22                                // 000000001010: 02282D15
+\t{insn}
+\ts_waitcnt lgkmcnt(1)                                        // 00000000101C: BF8C017F
+\tv_mul_f32_e32 v30, v10, v11                                // 000000001020: 0A3C150A
+\ts_waitcnt lgkmcnt(0)                                        // 000000001024: BF8C007F
+\tv_mul_f32_e32 v31, v14, v17                                // 000000001028: 0A3E230E
+\ts_endpgm                                                    // 00000000102C: BF810000
+"""
+
+
+def test_lds_window_check_flags_a_register_touched_before_its_wait():
+  ok = _SYNTH.format(insn='v_mov_b32_e32 v40, v41                                     // 000000001014: 7E500329')
+  assert lds_window_violations(_functions(ok)['srl_k_step']) == []
+  # a copy of a destination register of the first read before lgkmcnt(1) retires it
+  early = _SYNTH.format(insn='v_mov_b32_e32 v40, v12                                     // 000000001014: 7E50030C')
+  bad = lds_window_violations(_functions(early)['srl_k_step'])
+  assert [a for a, _ in bad] == [0x1000] and 'v_mov_b32_e32' in bad[0][1]
+  # the second read is retired only by lgkmcnt(0): a use between the two waits is flagged, the same use after it is not
+  late = _SYNTH.replace('v_mul_f32_e32 v30, v10, v11', 'v_mul_f32_e32 v30, v10, v15').format(insn='s_nop 0   // 000000001014: BF800000')
+  assert [a for a, _ in lds_window_violations(_functions(late)['srl_k_step'])] == [0x1008]
+  # a write to a destination register (a spill reload into it, say) is flagged as well, and so is a branch in the window
+  w = _SYNTH.format(insn='v_mov_b32_e32 v16, 0                                       // 000000001014: 7E200280')
+  assert [a for a, _ in lds_window_violations(_functions(w)['srl_k_step'])] == [0x1008]
+  br = _SYNTH.format(insn='s_cbranch_scc1 3                                           // 000000001014: BF850003 <srl_k_step+0x24>')
+  assert [a for a, _ in lds_window_violations(_functions(br)['srl_k_step'])] == [0x1000, 0x1008]

@@ -167,6 +167,7 @@ def test_two_wave_settle_variant_matches_the_oracle(ref_pool, oracle_mod, monkey
   monkeypatch.setenv('SRL_STEP_VARIANT', 'two_wave')
   L, n = 14, 5
   g, o = _mk(ref_pool, oracle_mod, n, L, seed=17)
+  assert g.step_variant() == (128, 2, 3)       # srl_k_step_t128 ran, not the default four-wave variant
   gout, oout = g.reset(), o.reset()
   assert np.array_equal(gout[0][0].cpu().numpy(), oout[0][0])
   for k in range(L + 1):
@@ -194,16 +195,23 @@ def test_ordered_launch_matches_the_oracle(ref_pool, oracle_mod, L, n, kw):
   g.close()
 
 
-@pytest.mark.parametrize('L,n,kw', [(8, 24, {}), (14, 6, {}), (20, 4, dict(resolution_factor=4))])
+@pytest.mark.parametrize('L,n,kw', [
+  (8, 24, {}), (14, 6, {}), (20, 4, dict(resolution_factor=4)),
+  (16, 6, dict(concurrent_envs=4096)),         # the two-wave variant (configs[2]'s shape): its StageLds over the scratch region
+  (9, 6, {}), (17, 4, {}),                     # the first lengths of the 9 - 16 and the 17 - 32 variants
+])
 def test_tail_staged_records_equal_the_staging_kernels(ref_pool, L, n, kw):
-  """The rocks' render records (csrc/stage.h) are made in the tail of the settle kernels (all three thread / point variants
-  here: 128 threads, 256 threads, 256 threads with two points per thread); `srl_k_stage` makes them for a handle whose
+  """The rocks' render records (csrc/stage.h) are made in the tail of the settle kernels (all four variants here: 128
+  threads, 256 threads, 256 threads with two points per thread, 128 threads with two points per thread — the last told
+  that 4,096 envs share the device); `srl_k_stage` makes them for a handle whose
   records are stale.  Two handles with the same seed, one of them told before every step that its bodies were moved
   (`set_body_state` with nothing to set: the records are staged again by the kernel after the settle kernel): the records of
   every placed rock, the observations and the rewards are equal bit for bit."""
   from stackrl_amd import env as envs
   a = envs.VecStackEnv(n_parallel=n, seed=13, pool=ref_pool, block=True, episode_length=L, **kw)
   b = envs.VecStackEnv(n_parallel=n, seed=13, pool=ref_pool, block=True, episode_length=L, **kw)
+  kernel = 0 if L <= 8 else 2 if L > 16 else 3 if kw.get('concurrent_envs', 0) >= 3072 else 1   # (srl_get_step_variant)
+  assert a.step_variant()[2] == kernel and b.step_variant()[2] == kernel
   a.reset(); b.reset()
   for k in range(L + 2):
     act = a.sample()
