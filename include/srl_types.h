@@ -30,6 +30,12 @@ extern "C" {
  * (not scaled). */
 enum { SRL_METRIC_IOU = 0, SRL_METRIC_OR = 1, SRL_METRIC_DIOU = 2, SRL_METRIC_DOR = 3, SRL_METRIC_ALL = 4, SRL_METRIC_EVAL = 5 };
 
+/* Observation element types, the `dtype` argument of StackEnv (env.py:24, :168-180), in the reference's order. */
+enum {
+  SRL_DTYPE_UINT8 = 0, SRL_DTYPE_UINT16 = 1, SRL_DTYPE_UINT32 = 2, SRL_DTYPE_UINT64 = 3,
+  SRL_DTYPE_FLOAT16 = 4, SRL_DTYPE_FLOAT32 = 5, SRL_DTYPE_FLOAT64 = 6
+};
+
 /* Return codes (the Python shim maps them to the reference's exception types:
  * AssertionError env.py:238, RuntimeError simulator.py:221-224, ValueError env.py:169). */
 enum {
@@ -94,6 +100,8 @@ typedef struct srl_config {
                                   episode_length * 2^k object maps, the maps of the n rocks still unplaced first (rock-major,
                                   orientation-minor, observer.py:310-327), empty maps after them;
                                   action = (rock * 2^k + orientation) * A + pixel with rock < n; 0 = Stack-v0 */
+  /* --- observation, env.py:168-180 --- */
+  int32_t obs_dtype;           /* SRL_DTYPE_*: element type of both observation tensors; Stack-v0 registry: uint8 */
 } srl_config;
 
 #ifdef __cplusplus

@@ -65,7 +65,12 @@ int srl_set_script(srl_env* env, const int32_t* mesh_ids, const int32_t* goal_re
  * observable orientation (the overhead map is returned once, not 2^k copies as env.py:472-480 stacks them).
  * With ordering_freedom = 1 (`TestSimulator`, simulator.py:343-378) obs_obj is u8[n][L * 2^k][h][w][1]: the maps of the
  * rocks still unplaced first (rock-major, orientation-minor, observer.py:310-327), empty maps after them — the fixed-size
- * form of the reference's shrinking list (env.py:596-608). */
+ * form of the reference's shrinking list (env.py:596-608).
+ * Element type: "u8" above is cfg->obs_dtype's (srl_config, SRL_DTYPE_*; the reference's `dtype`, env.py:168-180), so the
+ * per-env strides of both buffers are those counts times the element size: uint16 / float16 2 bytes, uint32 / float32 4,
+ * uint64 / float64 8.  Integer types hold x * (2^k - 1) / max(max_z, object_max_dimension) in float32, truncated as numpy
+ * does on x86-64 (a height equal to that maximum is 0 in uint32 / uint64: float32(2^k - 1) = 2^k wraps, DESIGN.md
+ * section 5); float types hold the float32 map values (float16 rounded to nearest even).  The same holds for srl_step. */
 int srl_reset(srl_env* env, void* obs_map_dev, void* obs_obj_dev, void* stream);
 
 /* `ParallelEnv.step` (utils.py:468-486): action int64[n]; reward float[n] (float[n][4] with metric 'all' = IoU, OR, DIoU,

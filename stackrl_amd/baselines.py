@@ -35,6 +35,10 @@ def heuristic_values(method, inputs, mask=True, difference_exponent=2, weights_e
                      threshold=0.75, generator=None):
   """Value map float64 [B, OH, OW] of one method and (optionally) the goal-overlap mask bool [B, OH, OW]."""
   xm, xo = inputs
+  for x in (xm, xo):
+    if x.dtype != torch.uint8:    # the kernels read bytes (csrc/heuristics.hip)
+      raise ValueError('heuristic_values needs uint8 observations, got {} (an env built with dtype={!r})'.format(
+        x.dtype, str(x.dtype).replace('torch.', '')))
   if not xm.is_cuda:
     raise RuntimeError('heuristic_values needs a HIP device (no CPU fallback)')
   xm = xm.contiguous(); xo = xo.contiguous()

@@ -21,6 +21,8 @@ SOLVER_PRESETS = {
 }
 
 METRICS = {'iou': 0, 'or': 1, 'diou': 2, 'dor': 3, 'all': 4, 'eval': 5}  # rewarder.py:7-14
+# observation element types (env.py:24) -> SRL_DTYPE_* (include/srl_types.h), in the reference's order
+DTYPES = {'uint8': 0, 'uint16': 1, 'uint32': 2, 'uint64': 3, 'float16': 4, 'float32': 5, 'float64': 6}
 REWARD_KEYS = {4: ('IoU', 'OR', 'DIoU', 'DOR'), 5: ('IoU', 'AD')}      # the dict keys of rewarder.py:147-158
 
 # return codes, include/srl_types.h
@@ -61,6 +63,7 @@ class CConfig(ctypes.Structure):
     ('place_at_com', ctypes.c_int32),
     ('orientation_freedom', ctypes.c_int32),
     ('ordering_freedom', ctypes.c_int32),
+    ('obs_dtype', ctypes.c_int32),
   ]
 
 
@@ -105,9 +108,8 @@ class StackConfig:
   def __post_init__(self):
     if not 0 <= int(self.orientation_freedom) <= 4:
       raise ValueError('orientation_freedom must be in 0..4 (at most 16 orientations)')
-    if self.dtype != 'uint8':
-      # env.py:169-170 raises ValueError for unknown dtypes; the build implements the Stack-v0 one.
-      raise ValueError('Invalid value {} for argument dtype.'.format(self.dtype))
+    if self.dtype not in DTYPES:
+      raise ValueError('Invalid value {} for argument dtype.'.format(self.dtype))   # env.py:169-170
     if self.num_sim_steps:
       raise ValueError('num_sim_steps is not supported (the reference branch is broken, simulator.py:325-326).')
     if not self.flat_action:
@@ -199,6 +201,7 @@ class StackConfig:
       place_at_com=int(bool(self.place_at_com)),
       orientation_freedom=int(self.orientation_freedom),
       ordering_freedom=int(bool(self.ordering_freedom)),
+      obs_dtype=DTYPES[self.dtype],
     )
 
   @classmethod

@@ -14,9 +14,11 @@
 // broadcasts, packed FMAs, min3) and merge into the tile — as rows of the depth-codec table, which are monotone in the
 // height — with integer atomicMax -> one branch-free epilogue pass looks the reference's depth codec up
 // (observer.py:259-260, tabulated over the float32 lattice of 1000 - z: DevParams::codec), streams out
-// H (16 B per lane, 1 KB contiguous per wave store), the packed uint8 observation (env.py:171-172, :228-231) and
+// H (16 B per lane, 1 KB contiguous per wave store), the packed observation (env.py:168-180, :228-231: uint8, or one of
+// the reference's six other dtypes through a kernel of its own — obs_code below, with the uint32 / uint64 wrap quirk) and
 // accumulates the IoU sums (rewarder.py:297-307) in the fixed order DESIGN.md defines.  HBM traffic per env step
-// is the algorithmic 6*res^2 + 5*r^2 bytes out plus ~1.4 KB per rock of mesh/pose data in (L2-resident pool).
+// is the algorithmic (4 + 2s)*res^2 + (4 + s)*r^2 bytes out (s = the element size, 1 for uint8) plus ~1.4 KB per rock of
+// mesh/pose data in (L2-resident pool).
 //
 // K3: per-mesh underside map rendered once at srl_load_meshes and cached: it depends only on the mesh
 // (spawn orientation is the identity, env.py:120-121).
@@ -43,24 +45,61 @@ __device__ __forceinline__ float elev_object(const DevParams& P, float d) {
   return P.obj_c1 - P.obj_c2 / (SRL_FAR + P.c.object_max_dimension * (0.5f - d));
 }
 
+// ---- observation element types (env.py:168-180 `_return`; DESIGN.md section 5, "Observation dtypes").  With den =
+//      max(max_z, object_max_dimension) the reference returns np.array(x * (2^k - 1) / den, uintK) — evaluated in float32
+//      (a python scalar does not widen a float32 array), then truncated — and np.array(x, floatK) for the float types.
+//      A value enters the output as a 32-bit CODE, evaluated once per codec-table row / constant (srl_k_codec_table) and,
+//      for the object maps, per pixel from the float cache:
+//        uint8 / uint16 / uint32: the integer itself;  float16: the half's bits;  float32 / float64: the float32 bits of x;
+//        uint64: the float32 bits of y = x * (2^64 - 1) / den (the stores make the integer, obs_u64).
+//      Reference quirk, reproduced on purpose: float32(2^32 - 1) and float32(2^64 - 1) are 2^32 and
+//      2^64, so a pixel with x == den (the height map saturates at max_z, and den == max_z whenever max_z >=
+//      object_max_dimension) gives y == 2^k, which numpy on x86-64 converts to 0: it truncates toward zero and keeps the low k
+//      bits.  The device's v_cvt_u32_f32 saturates instead, so the conversions below go through int64 (uint32) or test for
+//      2^64 (uint64).  y never exceeds 2^k: x <= den and rounding is monotone.
+__device__ __forceinline__ uint32_t obs_code(int dt, float x, float den) {
+  switch (dt) {
+    case SRL_DTYPE_UINT16: return (uint32_t)(uint16_t)(int64_t)((x * 65535.0f) / den);
+    case SRL_DTYPE_UINT32: return (uint32_t)(int64_t)((x * (float)0xffffffffu) / den);                 // (2^32 -> 0)
+    case SRL_DTYPE_UINT64: return __float_as_uint((x * (float)0xffffffffffffffffull) / den);
+    case SRL_DTYPE_FLOAT16: return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x);            // round to nearest even
+    case SRL_DTYPE_FLOAT32:
+    case SRL_DTYPE_FLOAT64: return __float_as_uint(x);
+    default: return (uint32_t)(uint8_t)((x * 255.0f) / den);                                         // env.py:171-172
+  }
+}
+// the uint64 element of a code (the float32 y above): truncation toward zero, low 64 bits kept — y = 2^64 gives 0
+__device__ __forceinline__ uint64_t obs_u64(uint32_t code) {
+  const float y = __uint_as_float(code);
+  return y >= 0x1p64f ? 0ull : y >= 0.0f ? (uint64_t)y : (uint64_t)(int64_t)y;
+}
+template <int DT> struct ObsElem { static constexpr int size = 1; };
+template <> struct ObsElem<SRL_DTYPE_UINT16> { static constexpr int size = 2; };
+template <> struct ObsElem<SRL_DTYPE_FLOAT16> { static constexpr int size = 2; };
+template <> struct ObsElem<SRL_DTYPE_UINT32> { static constexpr int size = 4; };
+template <> struct ObsElem<SRL_DTYPE_FLOAT32> { static constexpr int size = 4; };
+template <> struct ObsElem<SRL_DTYPE_UINT64> { static constexpr int size = 8; };
+template <> struct ObsElem<SRL_DTYPE_FLOAT64> { static constexpr int size = 8; };
+
 // the overhead depth codec tabulated over the lattice of t = fl(FAR - z) (see DevParams::codec): row 0 holds the
-// elevation bits and the observation byte of a pixel that saw no rock, row v in 1 .. n those for t = near + (n - v) 2^-14
+// elevation bits and the observation code of a pixel that saw no rock, row v in 1 .. n those for t = near + (n - v) 2^-14
 extern "C" __global__ void __launch_bounds__(256) srl_k_codec_table(DevParams P, uint2* __restrict__ tab, int n) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   const float nearp = SRL_FAR - P.c.max_z;
   const float den = fmaxf(P.c.max_z, P.c.object_max_dimension);
-  if (v == n + 1) {   // goal-channel bytes (env.py:171-172 applied to the goal height and to 0)
-    tab[v] = make_uint2((uint32_t)(uint8_t)((P.goal_z * 255.0f) / den), (uint32_t)(uint8_t)((0.0f * 255.0f) / den));
+  const int dt = P.c.obs_dtype;
+  if (v == n + 1) {   // goal-channel codes (env.py:168-180 applied to the goal height and to 0)
+    tab[v] = make_uint2(obs_code(dt, P.goal_z, den), obs_code(dt, 0.0f, den));
     return;
   }
-  if (v == n + 2) {   // byte of an empty object-map pixel
-    tab[v] = make_uint2((uint32_t)(uint8_t)((elev_object(P, 1.0f) * 255.0f) / den), 0u);
+  if (v == n + 2) {   // code of an empty object-map pixel
+    tab[v] = make_uint2(obs_code(dt, elev_object(P, 1.0f), den), 0u);
     return;
   }
   if (v > n) return;
   const float t = v > 0 ? nearp + (float)(n - v) * (1.0f / 16384.0f) : SRL_FAR - 0.0f;   // exact: a lattice point of [512, 1024]
   const float hh = elev_overhead(P, depth_encode(t, nearp, SRL_FAR));
-  tab[v] = make_uint2(__float_as_uint(hh), (uint32_t)(uint8_t)((hh * 255.0f) / den));
+  tab[v] = make_uint2(__float_as_uint(hh), obs_code(dt, hh, den));
 }
 
 // reference evaluation over an unsorted plane list (K3); K2 uses the type-sorted loops below.
@@ -242,6 +281,60 @@ __device__ __forceinline__ void out_u2(uint8_t* base, int g, uint2 v) {
   ((uint2*)base)[g] = v;
 #endif
 }
+// NT = false: a plain store.  The observation of a 4-pixel group is 32 or 64 bytes for 4- and 8-byte elements, written by
+// 2 or 4 stores of 16 bytes, so that each store instruction of a wave covers only every second (fourth) 16-byte piece of
+// its span: non-temporal, those partial lines cost 75 / 415 us per launch at 1,024 envs x 8 rocks (float32 / uint64),
+// plain ones 47 / 100 us — L2 completes the lines before it writes them back (profiles/render_obs_dtypes.txt).
+typedef unsigned int nt_u4 __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ void out_u4(uint8_t* base, int g, uint4 v) {
+#ifndef SRL_PLAIN_STORES
+  if (NT) { __builtin_nontemporal_store((nt_u4){v.x, v.y, v.z, v.w}, (nt_u4*)base + g); return; }
+#endif
+  ((uint4*)base)[g] = v;
+}
+__device__ __forceinline__ uint4 u64_pair(uint64_t a, uint64_t b) {
+  return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+}
+__device__ __forceinline__ uint64_t f64_bits(uint32_t code) { return (uint64_t)__double_as_longlong((double)__uint_as_float(code)); }
+
+// The observation of pixel group g (4 pixels x (height, goal) = 8 elements) in a type other than uint8: h = the pixels' codes,
+// bit t of gm = pixel t lies in the goal rectangle (goal code gc, else zc).  16-byte stores: one non-temporal store for 2-byte
+// elements (a wave's store is contiguous), two plain ones for 4-byte and four for 8-byte ones (see out_u4).
+template <int DT>
+__device__ __forceinline__ void out_obs(uint8_t* base, int g, const uint32_t (&h)[4], uint32_t gm, uint32_t gc, uint32_t zc) {
+  uint32_t c[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) c[t] = zc ^ ((gc ^ zc) & (uint32_t)__builtin_amdgcn_sbfe((int)gm, t, 1));
+  if constexpr (ObsElem<DT>::size == 2) {
+    out_u4<true>(base, g, make_uint4(h[0] | (c[0] << 16), h[1] | (c[1] << 16), h[2] | (c[2] << 16), h[3] | (c[3] << 16)));
+  } else if constexpr (ObsElem<DT>::size == 4) {
+    out_u4<false>(base, 2 * g, make_uint4(h[0], c[0], h[1], c[1]));
+    out_u4<false>(base, 2 * g + 1, make_uint4(h[2], c[2], h[3], c[3]));
+  } else if constexpr (DT == SRL_DTYPE_UINT64) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) out_u4<false>(base, 4 * g + t, u64_pair(obs_u64(h[t]), obs_u64(c[t])));
+  } else {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) out_u4<false>(base, 4 * g + t, u64_pair(f64_bits(h[t]), f64_bits(c[t])));
+  }
+}
+
+// The object observation in a type other than uint8: pixels 4 idx .. 4 idx + 3 of a map, from their codes
+template <int DT>
+__device__ __forceinline__ void out_obj(uint8_t* base, size_t idx, const uint32_t (&h)[4]) {
+  if constexpr (ObsElem<DT>::size == 2) {
+    ((uint2*)base)[idx] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+  } else if constexpr (ObsElem<DT>::size == 4) {
+    ((uint4*)base)[idx] = make_uint4(h[0], h[1], h[2], h[3]);
+  } else if constexpr (DT == SRL_DTYPE_UINT64) {
+    ((uint4*)base)[2 * idx] = u64_pair(obs_u64(h[0]), obs_u64(h[1]));
+    ((uint4*)base)[2 * idx + 1] = u64_pair(obs_u64(h[2]), obs_u64(h[3]));
+  } else {
+    ((uint4*)base)[2 * idx] = u64_pair(f64_bits(h[0]), f64_bits(h[1]));
+    ((uint4*)base)[2 * idx + 1] = u64_pair(f64_bits(h[2]), f64_bits(h[3]));
+  }
+}
 
 // min with the lane a DPP control selects (0xB1: lane ^ 1, 0x4E: lane ^ 2 within quads; 0x141: mirror within half rows)
 template <int CTRL>
@@ -314,11 +407,13 @@ extern "C" __global__ void __launch_bounds__(256) srl_k_stage(DevParams P, float
 }
 
 // poses_ext != nullptr: test/profiling hook rendering explicit poses (srl_render_heightmap)
-extern "C" __global__ void __launch_bounds__(SRL_RENDER_THREADS, 4)
-srl_k_render(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* __restrict__ obs_map,
-             uint8_t* __restrict__ obs_obj, float* __restrict__ reward, uint8_t* __restrict__ done,
-             const int32_t* __restrict__ nb_ext, float* __restrict__ height_ext) {
+// DT: the observation's element type (SRL_DTYPE_*); one kernel per type (srl_k_render = uint8, srl_k_render_u16 ...)
+template <int DT>
+__device__ __forceinline__ void render_body(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* __restrict__ obs_map,
+                                            uint8_t* __restrict__ obs_obj, float* __restrict__ reward, uint8_t* __restrict__ done,
+                                            const int32_t* __restrict__ nb_ext, float* __restrict__ height_ext) {
   extern __shared__ float4 lds_raw[];
+  constexpr int ES = ObsElem<DT>::size;
 #ifdef SRL_ABL_EMPTY
   if (P.px != 12345.0f) return;
 #endif
@@ -395,7 +490,7 @@ srl_k_render(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* 
   const uint32_t gbyte = P.gbyte, zbyte = P.zbyte, b_empty = P.b_empty;   // (DevParams: evaluated once on the device)
   const float h_empty = P.h_empty;
   float* Hout = ext ? height_ext + (size_t)e * npx : P.H + (size_t)e * npx;
-  uint8_t* om = ext ? nullptr : obs_map + (size_t)e * npx * 2;
+  uint8_t* om = ext ? nullptr : obs_map + (size_t)e * npx * 2 * ES;
   const int ngroups4 = npx / 4, nrounds = (ngroups4 + SRL_RENDER_THREADS - 1) / SRL_RENDER_THREADS;
   // pixel-group walk of a thread: group g = tid + 512 k holds pixels 4 g .. 4 g + 3 = row i, columns jb .. jb + 3
   // (res is a multiple of 8); from one round to the next the group advances by di rows and dj columns
@@ -418,12 +513,31 @@ srl_k_render(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* 
     // the pending rock's maps, or with ordering freedom (observer.py:310-327) those of the rocks still unplaced, in list
     // order, then empty maps; bytes from the per-mesh cache, four pixels per lane (the map size is a multiple of 4)
     const int shown = P.c.ordering_freedom ? P.c.episode_length : 1;
-    uint32_t* oo = (uint32_t*)(obs_obj + (size_t)e * rr * shown);
-    const uint32_t eb4 = P.obj_empty_byte * 0x01010101u;
-    for (int k = 0; k < shown; ++k) {
-      const int m = P.c.ordering_freedom ? (k < left ? h->ids[k] : -1) : pending;
-      const uint32_t* src = (const uint32_t*)(P.objmap_u8 + (size_t)(m < 0 ? 0 : m) * rr);
-      for (int idx = tid; idx < rr / 4; idx += SRL_RENDER_THREADS) oo[(size_t)k * (rr / 4) + idx] = m >= 0 ? src[idx] : eb4;
+    if constexpr (DT == SRL_DTYPE_UINT8) {
+      uint32_t* oo = (uint32_t*)(obs_obj + (size_t)e * rr * shown);
+      const uint32_t eb4 = P.obj_empty_byte * 0x01010101u;
+      for (int k = 0; k < shown; ++k) {
+        const int m = P.c.ordering_freedom ? (k < left ? h->ids[k] : -1) : pending;
+        const uint32_t* src = (const uint32_t*)(P.objmap_u8 + (size_t)(m < 0 ? 0 : m) * rr);
+        for (int idx = tid; idx < rr / 4; idx += SRL_RENDER_THREADS) oo[(size_t)k * (rr / 4) + idx] = m >= 0 ? src[idx] : eb4;
+      }
+    } else {
+      // other types: codes of the float cache's values (no cache per type), the empty map's code from DevParams
+      uint8_t* oo = obs_obj + (size_t)e * rr * shown * ES;
+      const float den = fmaxf(P.c.max_z, P.c.object_max_dimension);
+      const uint32_t ec = P.obj_empty_byte;
+      for (int k = 0; k < shown; ++k) {
+        const int m = P.c.ordering_freedom ? (k < left ? h->ids[k] : -1) : pending;
+        const float4* src = (const float4*)(P.objmap + (size_t)(m < 0 ? 0 : m) * rr);
+        for (int idx = tid; idx < rr / 4; idx += SRL_RENDER_THREADS) {
+          uint32_t c[4] = {ec, ec, ec, ec};
+          if (m >= 0) {
+            const float4 v = src[idx];
+            c[0] = obs_code(DT, v.x, den); c[1] = obs_code(DT, v.y, den); c[2] = obs_code(DT, v.z, den); c[3] = obs_code(DT, v.w, den);
+          }
+          out_obj<DT>(oo, (size_t)k * (rr / 4) + idx, c);
+        }
+      }
     }
   }
 #endif
@@ -470,7 +584,11 @@ srl_k_render(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* 
           else {
 #ifndef SRL_ABL_NOSTORE
             out_f4(Hout, g, he4);
-            if (om) out_u2(om, g, make_uint2(rowin ? w_in_lo : w_out, rowin ? w_in_hi : w_out));
+            if constexpr (DT == SRL_DTYPE_UINT8) {
+              if (om) out_u2(om, g, make_uint2(rowin ? w_in_lo : w_out, rowin ? w_in_hi : w_out));
+            } else {
+              if (om) out_obs<DT>(om, g, {b_empty, b_empty, b_empty, b_empty}, rowin ? colmask : 0u, gbyte, zbyte);
+            }
 #endif
           }
         }
@@ -490,7 +608,11 @@ srl_k_render(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* 
         else {
 #ifndef SRL_ABL_NOSTORE
           out_f4(Hout, g, he4);
-          if (om) out_u2(om, g, make_uint2((epair | zpair) ^ goal_pair(inm, gdiff), (epair | zpair) ^ goal_pair(inm >> 2, gdiff)));
+          if constexpr (DT == SRL_DTYPE_UINT8) {
+            if (om) out_u2(om, g, make_uint2((epair | zpair) ^ goal_pair(inm, gdiff), (epair | zpair) ^ goal_pair(inm >> 2, gdiff)));
+          } else {
+            if (om) out_obs<DT>(om, g, {b_empty, b_empty, b_empty, b_empty}, inm, gbyte, zbyte);
+          }
 #endif
         }
         jb += walk_dj; i += walk_di;
@@ -687,6 +809,7 @@ srl_k_render(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* 
         // rewarder.py:297-307: goal pixels add min / max(h, goal) to the two sums, the others max(h, 0) to the union
         // only (x + 0 = x bit for bit here: the partial sums never hold -0); m = all ones on a goal pixel
         uint32_t glo = 0u, ghi = 0u;   // goal-channel bits of the two observation words
+        uint32_t gm = 0u;              // (other types: bit t = pixel t lies in the goal rectangle)
         const bool rowin = (unsigned)(i - g0) < (unsigned)g2;
         if (aligned && __builtin_amdgcn_ballot_w64(rowin && colmask != 0u) == 0ull) {
           // none of the wave's groups of this round touches the goal (a wave covers whole rows): union sum only
@@ -702,11 +825,16 @@ srl_k_render(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* 
           }
           if (aligned) { glo = rowin ? gp_lo : 0u; ghi = rowin ? gp_hi : 0u; }
           else { glo = goal_pair(inm, gdiff); ghi = goal_pair(inm >> 2, gdiff); }
+          gm = inm;
         }
 #ifndef SRL_ABL_NOSTORE
         if (covg) {
           out_f4(Hout, g, make_float4(hv[0], hv[1], hv[2], hv[3]));
-          if (om) out_u2(om, g, make_uint2((hb[0] | (hb[1] << 16) | zpair) ^ glo, (hb[2] | (hb[3] << 16) | zpair) ^ ghi));
+          if constexpr (DT == SRL_DTYPE_UINT8) {
+            if (om) out_u2(om, g, make_uint2((hb[0] | (hb[1] << 16) | zpair) ^ glo, (hb[2] | (hb[3] << 16) | zpair) ^ ghi));
+          } else {
+            if (om) out_obs<DT>(om, g, hb, gm, gbyte, zbyte);
+          }
         }
 #else
         if (covg && hv[0] == 12345.0f && hb[0] == 77u) ((float4*)Hout)[g] = make_float4(hv[0], hv[1], hv[2], hv[3]);
@@ -771,6 +899,20 @@ srl_k_render(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* 
   }
   RSTAMP(6);
 }
+
+#define SRL_RENDER_KERNEL(name, DT)                                                                                       \
+  extern "C" __global__ void __launch_bounds__(SRL_RENDER_THREADS, 4)                                                     \
+  name(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* __restrict__ obs_map, uint8_t* __restrict__ obs_obj, \
+       float* __restrict__ reward, uint8_t* __restrict__ done, const int32_t* __restrict__ nb_ext, float* __restrict__ height_ext) { \
+    render_body<DT>(P, stage, slots, obs_map, obs_obj, reward, done, nb_ext, height_ext);                                 \
+  }
+SRL_RENDER_KERNEL(srl_k_render, SRL_DTYPE_UINT8)
+SRL_RENDER_KERNEL(srl_k_render_u16, SRL_DTYPE_UINT16)
+SRL_RENDER_KERNEL(srl_k_render_u32, SRL_DTYPE_UINT32)
+SRL_RENDER_KERNEL(srl_k_render_u64, SRL_DTYPE_UINT64)
+SRL_RENDER_KERNEL(srl_k_render_f16, SRL_DTYPE_FLOAT16)
+SRL_RENDER_KERNEL(srl_k_render_f32, SRL_DTYPE_FLOAT32)
+SRL_RENDER_KERNEL(srl_k_render_f64, SRL_DTYPE_FLOAT64)
 
 // K3: underside map of one mesh at the spawn pose, in one observable orientation (blockIdx.y; Stack-v0 has only the
 // identity).  One workgroup per (mesh, orientation).  The rock turns about its link-frame origin, which sits at the

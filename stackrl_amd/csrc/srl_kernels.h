@@ -79,7 +79,8 @@ struct DevParams {
   int32_t codec_n;
   // constants of the render epilogue, evaluated once on the device by the expressions the oracle uses (rows 0, n + 1 and
   // n + 2 of the codec table) and read back by srl_create: elevation / observation byte of a pixel that saw no rock,
-  // goal and zero bytes of the goal channel (env.py:171-172), byte of an empty object-map pixel
+  // goal and zero bytes of the goal channel (env.py:171-172), byte of an empty object-map pixel.  With an obs_dtype other
+  // than uint8 the "bytes" here and in the codec table are that type's 32-bit codes (render.hip obs_code).
   float h_empty;
   uint32_t b_empty, gbyte, zbyte, obj_empty_byte;
   // walk of a thread over its pixel groups (group g = tid + 512 k = row i, columns jb .. jb + 3): per round +walk_di

@@ -96,6 +96,7 @@ int derive(DevParams& P) {
   if (c.overhead_res < c.object_res || c.object_res < 2 || c.overhead_res > 256 || (c.overhead_res % 8) != 0)
     return fail(SRL_EINVAL, "bad resolutions (overhead_res must be a multiple of 8, <= 256)");
   if (c.metric < 0 || c.metric > SRL_METRIC_EVAL) return fail(SRL_EINVAL, "Invalid value for argument metric");
+  if (c.obs_dtype < SRL_DTYPE_UINT8 || c.obs_dtype > SRL_DTYPE_FLOAT64) return fail(SRL_EINVAL, "Invalid value for argument dtype.");
   P.px = c.object_max_dimension / (float)c.object_res;
   P.inv_px = (float)c.object_res / c.object_max_dimension;
   P.lin_damp = (float)pow(1.0 - (double)c.linear_damping, (double)c.sim_time_step);
@@ -232,6 +233,11 @@ bool launch_ordered(const srl_env* env) {
   return env->order_mode == 1 || (env->order_mode < 0 && n >= SRL_ORDER_MIN_ENVS);
 }
 
+// the render kernel of each observation element type, indexed by SRL_DTYPE_* (render.hip SRL_RENDER_KERNEL)
+typedef void (*render_kernel_t)(DevParams, const float4*, int, uint8_t*, uint8_t*, float*, uint8_t*, const int32_t*, float*);
+const render_kernel_t k_render_of_dtype[SRL_DTYPE_FLOAT64 + 1] = {srl_k_render, srl_k_render_u16, srl_k_render_u32, srl_k_render_u64,
+                                                                  srl_k_render_f16, srl_k_render_f32, srl_k_render_f64};
+
 int launch_step_render(srl_env* env, const int64_t* action, void* obs_map, void* obs_obj, float* reward, uint8_t* done,
                        hipStream_t st, int force_reset) {
   if (!env->d_mh) return fail(SRL_ENOMESH, "srl_load_meshes must be called first");
@@ -270,8 +276,12 @@ int launch_step_render(srl_env* env, const int64_t* action, void* obs_map, void*
                (const int32_t*)nullptr, (const int32_t*)nullptr);
     env->stage_dirty = false;
   }
-  SRL_LAUNCH(env, 1, srl_k_render, dim3(n), dim3(SRL_RENDER_THREADS), env->render_lds, st, P, (const float4*)env->d_stage, L,
-             (uint8_t*)obs_map, (uint8_t*)obs_obj, reward, done, (const int32_t*)nullptr, (float*)nullptr);
+  if (P.c.obs_dtype == SRL_DTYPE_UINT8)   // (the Stack-v0 registry's type: the kernel by name, as before)
+    SRL_LAUNCH(env, 1, srl_k_render, dim3(n), dim3(SRL_RENDER_THREADS), env->render_lds, st, P, (const float4*)env->d_stage, L,
+               (uint8_t*)obs_map, (uint8_t*)obs_obj, reward, done, (const int32_t*)nullptr, (float*)nullptr);
+  else
+    SRL_LAUNCH(env, 1, k_render_of_dtype[P.c.obs_dtype], dim3(n), dim3(SRL_RENDER_THREADS), env->render_lds, st, P,
+               (const float4*)env->d_stage, L, (uint8_t*)obs_map, (uint8_t*)obs_obj, reward, done, (const int32_t*)nullptr, (float*)nullptr);
   HIP_TRY(hipGetLastError());
   return SRL_OK;
 }
@@ -305,6 +315,7 @@ int srl_config_default(srl_config* c) {
   c->place_at_com = 1;
   c->orientation_freedom = 0;
   c->ordering_freedom = 0;
+  c->obs_dtype = SRL_DTYPE_UINT8;    // Stack-v0 registry: dtype='uint8' (envs/stack/__init__.py:4-8)
   return SRL_OK;
 }
 
@@ -502,6 +513,8 @@ int srl_load_meshes(srl_env* env, const float* verts, const int32_t* vert_off, c
   HIP_TRY(hipFuncSetAttribute((const void*)srl_k_step_pp2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->step_lds));
   HIP_TRY(hipFuncSetAttribute((const void*)srl_k_step_t128, hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->step_lds));
   HIP_TRY(hipFuncSetAttribute((const void*)srl_k_render, hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->render_lds));
+  if (P.c.obs_dtype != SRL_DTYPE_UINT8)
+    HIP_TRY(hipFuncSetAttribute((const void*)k_render_of_dtype[P.c.obs_dtype], hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->render_lds));
   // K3: object maps of the whole pool, once
   hipLaunchKernelGGL(srl_k_objmap, dim3(n_mesh, P.n_orient), dim3(256), env->objmap_lds, 0, P, env->d_objmap, env->d_objmap_u8);
   HIP_TRY(hipGetLastError());

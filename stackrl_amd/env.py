@@ -4,8 +4,9 @@
 the reference (`stackrl/envs/utils.py:44-141` -> `ParallelEnv`, `:302-576`): same method and property
 names (`step/reset/sample/seed/close/__call__`, `batch_size`, `observation_spec`, `action_spec`,
 `multiprocessing`), same argument meaning, same tuple layout
-`((u8[B,H,W,2], u8[B,h,w,1]), f32[B], bool[B])`, same non-blocking default (a callable that yields the
-time step, `utils.py:468-486`), same exception types.  Tensors are torch (ROCm) instead of tf.
+`((u8[B,H,W,2], u8[B,h,w,1]), f32[B], bool[B])` (u8: the `dtype` argument's type, uint8 by default), same
+non-blocking default (a callable that yields the time step, `utils.py:468-486`), same exception types.  Tensors are torch
+(ROCm) instead of tf.
 
 All arithmetic happens in libstackrl_hip.so; torch only owns device memory and streams.
 """
@@ -22,6 +23,10 @@ from stackrl_amd import config as _config
 from stackrl_amd.config import StackConfig
 
 TensorSpec = collections.namedtuple('TensorSpec', ['shape', 'dtype'])
+
+# the observation's element type per `dtype` argument (env.py:24, :168-180; StackConfig.dtype)
+TORCH_DTYPES = {'uint8': torch.uint8, 'uint16': torch.uint16, 'uint32': torch.uint32, 'uint64': torch.uint64,
+                'float16': torch.float16, 'float32': torch.float32, 'float64': torch.float64}
 
 
 def _check(rc):
@@ -87,8 +92,9 @@ class VecStackEnv(object):
     B, H, h = self.config.n_envs, self.config.overhead_res, self.config.object_res
     # TestStackEnv (env.py:443-470): one object map per observable orientation, action = orientation * A + pixel
     self._no = self.config.n_object_maps   # with ordering freedom: the maps of every rock of the episode (empty once placed)
-    self._observation_spec = (TensorSpec((H, H, 2), torch.uint8),
-                              TensorSpec((h, h, 1) if self._no == 1 else (self._no, h, h, 1), torch.uint8))
+    dt = TORCH_DTYPES[self.config.dtype]   # both tensors, env.py:182-205
+    self._observation_spec = (TensorSpec((H, H, 2), dt),
+                              TensorSpec((h, h, 1) if self._no == 1 else (self._no, h, h, 1), dt))
     self._action_spec = TensorSpec((), torch.int64)
     self._B, self._H, self._hh = B, H, h
     self._closed = False
@@ -174,8 +180,9 @@ class VecStackEnv(object):
       torch.cuda.current_stream(self._device).wait_stream(self._side)
 
   def _new_obs(self):
-    return (torch.empty((self._B, self._H, self._H, 2), dtype=torch.uint8, device=self._device),
-            torch.empty((self._B,) + tuple(self._observation_spec[1].shape), dtype=torch.uint8, device=self._device))
+    dt = self._observation_spec[0].dtype
+    return (torch.empty((self._B, self._H, self._H, 2), dtype=dt, device=self._device),
+            torch.empty((self._B,) + tuple(self._observation_spec[1].shape), dtype=dt, device=self._device))
 
   def _finish(self, out):
     def wait():
@@ -456,9 +463,10 @@ class PipelinedVecStackEnv(object):
   def _outputs(self):
     e0 = self._envs[0]
     keys = self.config.reward_keys
+    dt = e0._observation_spec[0].dtype
     return dict(
-      om=torch.empty((self._B,) + tuple(e0._observation_spec[0].shape), dtype=torch.uint8, device=self._device),
-      oo=torch.empty((self._B,) + tuple(e0._observation_spec[1].shape), dtype=torch.uint8, device=self._device),
+      om=torch.empty((self._B,) + tuple(e0._observation_spec[0].shape), dtype=dt, device=self._device),
+      oo=torch.empty((self._B,) + tuple(e0._observation_spec[1].shape), dtype=dt, device=self._device),
       reward=torch.empty(self._B if keys is None else (self._B, len(keys)), dtype=torch.float32, device=self._device),
       done=torch.empty(self._B, dtype=torch.uint8, device=self._device), waits=[None] * self._K)
 
@@ -552,6 +560,10 @@ class StartedVecStackEnv(VecStackEnv):
         n_objects, episode_length))                                            # env.py:375-378
     self._random_lengths = bool(min_episode_length and min_episode_length < episode_length)
     self._lower, self._upper = int(n_objects) - int(episode_length), int(n_objects) - int(min_episode_length or 0)
+    dtype = kwargs.get('dtype', 'uint8')
+    if start_policy is None and dtype != 'uint8' and (self._upper if self._random_lengths else self._lower) > 0:
+      # the default start policy runs the heuristic kernels (csrc/heuristics.hip), which read uint8 observations
+      raise ValueError('The default start policy needs dtype uint8 observations (got {}): pass start_policy.'.format(dtype))
     super(StartedVecStackEnv, self).__init__(n_parallel=n_parallel, episode_length=n_objects, **kwargs)
     self._n_start_steps = int(n_objects) - int(episode_length)
     self._done_prev = None

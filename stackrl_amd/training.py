@@ -52,6 +52,12 @@ class Trainer(object):
     if isinstance(eval_env, types.GeneratorType):
       self._eval_curriculum = eval_env
       eval_env, _ = next(self._eval_curriculum)
+    for e in (env, eval_env):
+      # the Q-net's input scaling (nets.py) and the replay memory (dqn.py) take uint8 observations only; another dtype would
+      # be misread, not converted (models.py:144-147 divides by dtype.max: not built here)
+      dt = e.observation_spec[0].dtype if e is not None else None
+      if dt is not None and dt != torch.uint8:
+        raise ValueError('Training needs an env with dtype uint8 observations, got {}.'.format(str(dt).replace('torch.', '')))
     self._env, self._agent, self._eval_env = env, agent, eval_env
     self._directory = directory
     self._log_interval, self._eval_interval = int(log_interval), int(eval_interval)
@@ -284,8 +290,10 @@ class Trainer(object):
       new_env, self._current_goal = next(self._curriculum)
     except StopIteration:
       return False
-    assert (tuple(new_env.observation_spec[0].shape), tuple(new_env.observation_spec[1].shape)) == \
-           (tuple(self._env.observation_spec[0].shape), tuple(self._env.observation_spec[1].shape)), \
+    assert (tuple(new_env.observation_spec[0].shape), tuple(new_env.observation_spec[1].shape),
+            new_env.observation_spec[0].dtype) == \
+           (tuple(self._env.observation_spec[0].shape), tuple(self._env.observation_spec[1].shape),
+            self._env.observation_spec[0].dtype), \
       'All envs in curriculum must have same observation and action specs.'
     old, self._env = self._env, new_env
     getattr(old, 'close', lambda: None)()
