@@ -47,8 +47,19 @@ def test_xcorr_mfma_bf16_matches_torch(B, C, H, h):
   assert float((a - b).abs().max()) <= 4e-3 * float(b.abs().max())
 
 
-@pytest.mark.parametrize('B,C,H,h', [(3, 16, 128, 32), (4, 16, 64, 16), (2, 5, 128, 32)])
-@pytest.mark.parametrize('precision,tol', [(0, 6e-3), (1, 2e-5)])
+# Parameter lists as module constants: tests/test_update_dispatch.py (no GPU) imports them and checks that they reach every
+# dispatch regime of the Toeplitz kernel the product's update runs.
+XCORR_AUTOGRAD_CASES = [(3, 16, 128, 32), (4, 16, 64, 16), (2, 5, 128, 32)]
+XCORR_PRECISIONS = [(0, 6e-3), (1, 2e-5)]
+# The update's batch sizes (64 samples forward, 32 in all three modes: 4 and 2 channels per workgroup) in both geometries,
+# and ragged channel splits: 16 channels at 50 samples and 7 at 100 are 3 per workgroup with a last group of one
+XCORR_UPDATE_CASES = [(64, 16, 128, 32), (32, 16, 128, 32), (64, 16, 64, 16), (32, 16, 64, 16),
+                      (50, 16, 128, 32), (100, 7, 128, 32), (50, 16, 64, 16), (100, 7, 64, 16)]
+XCORR_ROWS_CASES = [(3, 16, 'f32x3'), (2, 7, 'f32x3'), (2, 16, 'f32'), (3, 16, 'bf16'), (200, 16, 'f32x3')]
+
+
+@pytest.mark.parametrize('B,C,H,h', XCORR_AUTOGRAD_CASES)
+@pytest.mark.parametrize('precision,tol', XCORR_PRECISIONS)
 def test_xcorr_mfma_autograd_matches_torch_fp64(B, C, H, h, precision, tol):
   """Forward and both gradients of the MFMA cross-correlation against the library formulation in fp64.
   Stated tolerances relative to each tensor's scale: 6e-3 with operands rounded to bf16, 2e-5 (the fp32 vector
@@ -67,6 +78,49 @@ def test_xcorr_mfma_autograd_matches_torch_fp64(B, C, H, h, precision, tol):
     assert got.shape == want.shape and got.dtype == torch.float32
     err = float((got.detach().double() - want.detach()).abs().max()); scale = float(want.detach().abs().max())
     assert err <= tol * scale, (err, scale)
+
+
+@pytest.mark.parametrize('B,C,H,h', XCORR_UPDATE_CASES)
+@pytest.mark.parametrize('precision,tol', XCORR_PRECISIONS)
+def test_xcorr_mfma_at_the_update_batch_sizes_matches_torch_fp64(B, C, H, h, precision, tol, monkeypatch):
+  """The three modes of the Toeplitz kernel with MORE THAN ONE CHANNEL PER WORKGROUP (`channel_split`; at 16 samples and
+  fewer a workgroup takes one channel and the channel loop runs once): the register prefetch of the next channel under the
+  current one's products, the accumulation over a workgroup's channels before `k_sum_partials`, the accumulator reset
+  between channels of the gradients, d/dx keeping the staged map over its channels — through the entry points and with the
+  operands `HandNet.backward` uses (`srl_tcorr_grad`'s zero-padded gradient map, `srl_tflip`'s flipped kernels), against the
+  library formulation with autograd in float64.  Tolerances as stated above; the inputs are non-negative maps and kernels
+  of mixed sign, so that a wrong or missing channel shows as an error of the order of the tensor's scale."""
+  from stackrl_amd import nets, qops, qtrain
+  L = qtrain._lib()
+  monkeypatch.setenv('SRL_XCORR_ROWS', '0')            # the Toeplitz kernel, whatever the batch size
+  g = torch.Generator(device='cuda').manual_seed(B * 13 + C + precision)
+  O = H - h + 1
+  x = torch.rand((B, C, H, H), generator=g, device='cuda')
+  w = torch.rand((B, C, h, h), generator=g, device='cuda') - 0.3
+  gpos = torch.randn((B, O, O, 16), generator=g, device='cuda')       # the gradient as it leaves pos_layers: channel 0 is d / d corr
+  out = qops.xcorr_forward_mfma(x, w, precision)
+  gcorr = torch.full((B, O, O), float('nan'), device='cuda')
+  gp = torch.full((B, O + 2 * (h - 1), O + 2 * (h - 1)), float('nan'), device='cuda')
+  wflip = torch.full((B, C, h, h), float('nan'), device='cuda')
+  assert L.srl_tcorr_grad(gpos.data_ptr(), 16, gcorr.data_ptr(), gp.data_ptr(), B, O, h - 1, qops._stream(gp)) == 0
+  assert L.srl_tflip(w.data_ptr(), wflip.data_ptr(), B * C, h * h, qops._stream(gp)) == 0
+  dx = qops._xcorr_mfma(1, precision, gp, wflip, B, C, H, h)
+  dw = qops._xcorr_mfma(2, precision, x, gcorr, B, C, H, h)
+  xd = x.double().requires_grad_(); wd = w.double().requires_grad_()
+  ref = nets.correlation_reference(xd, wd)
+  ref.backward(gpos[..., 0].double().reshape(B, 1, O, O))
+  figures = []
+  for name, got, want in (('forward', out, ref), ('d/dx', dx, xd.grad), ('d/dw', dw, wd.grad)):
+    assert got.shape == want.shape and got.dtype == torch.float32
+    err = float((got.double() - want.detach()).abs().max()); scale = float(want.detach().abs().max())
+    figures.append((name, err / scale))
+  print('xcorr', (B, C, H, h), 'precision', precision, figures)
+  for name, e in figures:
+    assert e <= tol, (name, e)
+  # fixed-order sums: bit-identical on repetition
+  assert torch.equal(out, qops.xcorr_forward_mfma(x, w, precision))
+  assert torch.equal(dx, qops._xcorr_mfma(1, precision, gp, wflip, B, C, H, h))
+  assert torch.equal(dw, qops._xcorr_mfma(2, precision, x, gcorr, B, C, H, h))
 
 
 @pytest.mark.parametrize('cin,cout,H', [(16, 16, 32), (16, 32, 16), (32, 16, 48), (32, 32, 16), (64, 32, 32), (64, 16, 16)])
@@ -314,6 +368,16 @@ def test_fast_rollout_follows_graph_replayed_updates(ref_pool):
 
 
 def test_train_step_matches_dqn_oracle():
+  _train_step_case(B=4, slots=8, mb=6)
+
+
+def test_train_step_at_minibatch_32_matches_dqn_oracle():
+  """The same at the product's minibatch size: the update's network passes at 64 / 32 / 32 samples inside `DQN.train` (64
+  stored transitions, at most one per env without a successor yet, so that 32 can be drawn without replacement)."""
+  _train_step_case(B=8, slots=8, mb=32)
+
+
+def _train_step_case(B, slots, mb):
   """One `DQN.train` step of the product settings (full-size net, MFMA cross-correlation, PER, Double-DQN, Huber) against
   oracle/dqn_oracle.py on the same minibatch: sampled indices (Gumbel top-k over the oracle's logits and the generator's
   own uniforms), importance weights, transitions, TD targets / loss / mean TD in float64, updated priorities and the
@@ -321,7 +385,7 @@ def test_train_step_matches_dqn_oracle():
   from oracle import dqn_oracle as O
   from stackrl_amd import nets
   from stackrl_amd.dqn import DQN
-  B, slots, mb, gamma, alpha, beta = 4, 8, 6, 0.9, 0.6, 0.5
+  gamma, alpha, beta = 0.9, 0.6, 0.5
   net = nets.DeepQSiamFCN(seed=3).cuda()
   agent = DQN(net, learning_rate=1e-4, adam_betas=(0.95, 0.95), minibatch_size=mb, replay_memory_size=B * slots,
               discount_factor=gamma, collect_batch_size=B, exploration=0.5, prioritization=alpha,
@@ -375,6 +439,7 @@ def test_train_step_matches_dqn_oracle():
   w0 = [p.detach().clone() for p in net.parameters()]
   loss, mtd = agent.train()                                    # samples the same minibatch (generator state restored)
   scale = max(1.0, float(np.abs(q).max()))
+  print('train step', (B, slots, mb), 'loss', float(loss), 'oracle', eloss, 'mean TD', float(mtd), 'oracle', emtd, 'scale', scale)
   assert abs(float(loss) - eloss) <= 2e-4 * max(eloss, 1e-3) + 1e-6 * scale
   assert abs(float(mtd) - emtd) <= 2e-4 * scale
   assert any(not torch.equal(a, b) for a, b in zip(w0, net.parameters()))
@@ -1058,7 +1123,7 @@ def test_rollout_argmax_against_float64_on_real_observations():
   assert b16['max_rel_err'] > x3['max_rel_err']              # (the labelled bf16 rollout is the narrower one)
 
 
-@pytest.mark.parametrize('B,C,dt', [(3, 16, 'f32x3'), (2, 7, 'f32x3'), (2, 16, 'f32'), (3, 16, 'bf16'), (200, 16, 'f32x3')])
+@pytest.mark.parametrize('B,C,dt', XCORR_ROWS_CASES)
 def test_xcorr_row_product_forward(B, C, dt, monkeypatch):
   """The rollout's cross-correlation forward as a product per map row (`k_xcorr_rows`, csrc/xcorr_mfma.hip: Hankel fragments of
   the row x the kernel's rows, the sum over kernel rows along a diagonal by DPP lane shifts): against the library formulation

@@ -18,43 +18,7 @@ import ctypes
 import numpy as np
 import pytest
 
-
-def wrw_tiles(taps, B, H, W):
-  if taps == 1:
-    return (B * H * W + 255) // 256
-  if W > 8 or H > 8:
-    return B * ((H + 15) // 16) * ((W + 15) // 16)
-  return ((B + 3) // 4) * ((H + 7) // 8) * ((W + 7) // 8)
-
-
-def wrw_groups(taps, B, H, W, cin, cout):
-  tiles = wrw_tiles(taps, B, H, W)
-  cot = 4 if cout % 64 == 0 else 2 if cout % 32 == 0 else 1
-  blocks = ((cin + 15) // 16) * (cout // (cot * 16))
-  return int(min(max(1024 // blocks, 1), tiles, 512)), cot
-
-
-def net_shapes():
-  """(taps, H, cin, cout) of every convolution `HandNet` differentiates (nets.py / layers.py:135-259) at 128 / 32 inputs."""
-  out = []
-  for res, cin0, depth in ((128, 2, 4), (32, 1, 2)):
-    c, r = cin0, res
-    for i in range(depth):
-      f = 16 * 2 ** i
-      out += [(9, r, c, f), (9, r, f, f)]
-      c, r = f, r // 2
-    fb = 16 * 2 ** depth
-    out += [(9, r, c, fb), (9, r, fb, fb)]
-    c = fb
-    for i in range(depth - 1, -1, -1):
-      f = 16 * 2 ** i
-      out.append((1, r, c, 4 * f))          # up{i}: 1 x 1 to 4 f channels (depth-to-space)
-      r *= 2
-      out += [(9, r, 2 * f, f), (9, r, f, f)]
-      c = f
-  out += [(9, 97, 1, 16), (9, 97, 16, 16)]     # pos_layers
-  return out
-
+from update_dispatch import net_shapes, wrw_groups, wrw_tiles      # shared with tests/test_update_dispatch.py
 
 SHAPES = [(9, 4, 8, 8, 256, 256)] + [(t, B, r, r, ci, co) for (t, r, ci, co) in net_shapes() for B in (32, 3)]
 
