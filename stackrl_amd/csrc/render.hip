@@ -28,9 +28,12 @@
 
 #define SRL_RENDER_THREADS 512
 
-// Diagnostic builds only (tools/stamps_render.py, tools/ab_render.py; the outputs of the ablations are wrong by design):
+// Diagnostic builds only (tools/stamps_render.py; tools/build_ablation_libs.sh for tools/ab_render.py — the outputs of the
+// ablations are wrong by design):
 //   SRL_STAMPS        per-phase wall-clock stamps of thread 0
 //   SRL_ABL_NOSTORE   no H / observation stores     SRL_ABL_NOCAST  no ray cast     SRL_ABL_NOSTAGE  no staging, no ray cast
+//   SRL_ABL_NOGOAL    no goal-rectangle masks       SRL_ABL_NOOBJ   no object observation
+//   SRL_ABL_NOTAIL    no reduction of the partial sums (no reward)
 //   SRL_ABL_EMPTY     the kernel returns at once (launch + event floor)
 #ifdef SRL_STAMPS
 #define RSTAMP(k) do { if (tid == 0) { long long _t = wall_clock64(); P.hdr[e].rstamps[k] += _t - _t0; _t0 = _t; } } while (0)
@@ -235,22 +238,14 @@ __device__ __forceinline__ void plane_sweep(const float4* pl, int n, int s, int 
     // of the list (min / max are idempotent: a plane met twice changes nothing).  No selects, no remainder loop.
     const int nbt = (n + 3) >> 2, last = n - 4;
     for (int t = s; t < nbt; t += 2 * S) {
-#ifdef SRL_ABL_NOPLANEREAD
-      const int oa = 0, ob = 4;   // (diagnostic: the same eight planes every trip, fetched once)
-#else
       const int oa = min(4 * t, last), ob = min(4 * (t + S), last);
-#endif
       float4 q0 = pl[oa], q1 = pl[oa + 1], q2 = pl[oa + 2], q3 = pl[oa + 3];
       float4 r0 = pl[ob], r1 = pl[ob + 1], r2 = pl[ob + 2], r3 = pl[ob + 3];
-#ifndef SRL_ABL_NOPLANEREAD
       asm volatile("" : "+v"(q0.w), "+v"(q1.w), "+v"(q2.w), "+v"(q3.w));   // keeps each fetch one 16-byte read
-#endif
       plane_eval<UP>(q0, py, vx, acc); plane_eval<UP>(q1, py, vx, acc);
       plane_eval<UP>(q2, py, vx, acc); plane_eval<UP>(q3, py, vx, acc);
-#ifndef SRL_ABL_NOPLANEREAD
       __builtin_amdgcn_sched_barrier(0);             // (the second batch arrives under the first one's arithmetic)
       asm volatile("" : "+v"(r0.w), "+v"(r1.w), "+v"(r2.w), "+v"(r3.w));
-#endif
       plane_eval<UP>(r0, py, vx, acc); plane_eval<UP>(r1, py, vx, acc);
       plane_eval<UP>(r2, py, vx, acc); plane_eval<UP>(r3, py, vx, acc);
     }
@@ -785,7 +780,6 @@ __device__ __forceinline__ void render_body(DevParams P, const float4* __restric
       const int g = tid + k * SRL_RENDER_THREADS;
       if (((todo >> k) & 1u) && g < ngroups4) {
         const bool covg = (cov >> k) & 1u;
-#ifndef SRL_ABL_NOCONSTROUND
         if (aligned && __builtin_amdgcn_ballot_w64(covg) == 0ull) {
           // no group of the wave holds a rock pixel this round (their H / observation bytes left with the early stores):
           // the sums take per-thread constants — no table look-ups, no stores
@@ -796,7 +790,6 @@ __device__ __forceinline__ void render_body(DevParams P, const float4* __restric
           if (jb >= res) { jb -= res; ++i; }
           continue;
         }
-#endif
         uint4 r4 = make_uint4(0u, 0u, 0u, 0u);   // codec-table rows of the four pixels (0: no rock)
         if (covg) r4 = ((const uint4*)L.tile)[g];
         const uint32_t rw[4] = {r4.x, r4.y, r4.z, r4.w};

@@ -49,11 +49,8 @@ __device__ __forceinline__ void srl_jitter_sync() {
 #define __syncthreads() srl_jitter_sync()
 #endif
 
-// lanes per manifold slot in the narrow phase: 32 in the 128-thread variant of <= 8 rocks, 16 where there are more slots than groups
-// (round 5, same box: 1,024 x 16 +1.6 %, 4,096 x 16 +2 %, the headline shape indifferent; bit-identical either way)
-#ifndef SRL_GJK_GROUP
-#define SRL_GJK_GROUP(T, PP) ((T) == 128 && (PP) == 1 ? 32 : 16)
-#endif
+// what distinguishes the four kernel variants <threads per env, pair points per thread>: defined beside their entry points
+template <int T, int PP> struct Variant;
 
 // Bodies (i < j) of pair id p = j (j - 1) / 2 + i, computed when the kernel fills its LDS table.  (Until round 3 this
 // was a pair of process-wide __constant__ tables that every srl_create rewrote: device state shared by all handles.)
@@ -81,13 +78,11 @@ struct Lds {
     const int blob = P->BLOB;
     oR = blob + P->S_R; oIW = blob + P->S_IW; oAMIN = blob + P->S_AMIN; oAMAX = blob + P->S_AMAX; oBC = blob + P->S_BC;
     oWV = blob + P->S_WV; oLV = blob + P->S_LV; oMISC = blob + P->S_MISC; oPAIR = blob + P->S_PAIR; vs3 = 3 * P->VS;
-#ifndef SRL_NO_LAUNDER
 #define SRL_KEEP(x) asm volatile("" : "+s"(x))
     SRL_KEEP(oX); SRL_KEEP(oQ); SRL_KEEP(oV); SRL_KEEP(oPX); SRL_KEEP(oPQ); SRL_KEEP(oMESH); SRL_KEEP(oGM);
     SRL_KEEP(oMAN); SRL_KEEP(oSOP); SRL_KEEP(oPOS); SRL_KEEP(oCOL); SRL_KEEP(oR); SRL_KEEP(oIW); SRL_KEEP(oAMIN);
     SRL_KEEP(oAMAX); SRL_KEEP(oBC); SRL_KEEP(oWV); SRL_KEEP(oLV); SRL_KEEP(oMISC); SRL_KEEP(oPAIR); SRL_KEEP(vs3);
 #undef SRL_KEEP
-#endif
   }
   __device__ __forceinline__ float* X(int b) const { return sm + oX + 4 * b; }
   __device__ __forceinline__ float* Q(int b) const { return sm + oQ + 4 * b; }
@@ -398,7 +393,7 @@ __device__ __forceinline__ void sat_faces(const DevParams& P, int mesh_a, const 
   dist = best;
 }
 
-// G lanes per slot (SRL_GJK_GROUP): GJK runs in lock step on all of them (support scans split), the first lane maintains
+// G lanes per slot (Variant::GJK_GROUP): GJK runs in lock step on all of them (support scans split), the first lane maintains
 // the manifold
 template <int G>
 __device__ __forceinline__ void narrowphase_slot(const Lds& L, int sl, int gl) {
@@ -736,18 +731,22 @@ __device__ __forceinline__ void cg_arrive(GRec& R, float& tie) {
                : "n"(LEFT));
 }
 
-template <bool WARM, bool AHEAD>
-__device__ __forceinline__ void ground_body(const Lds& L, GBody& gb, float& res) {
+// The ground phase of one body lane: its points in order on (v, w).  Without KEEP the pair is read from LDS here (AHEAD: in one go
+// with record 0) and written back, and the caller's v, w are scratch.  KEEP: it stays in the caller's registers from sweep to
+// sweep — sub-steps whose wave holds no pair point (half of all sub-steps, 20 - 85 % of the slowest envs') run their sweeps as the
+// ground phase alone, and nothing else reads or writes the velocities during the solve.
+template <bool WARM, bool AHEAD, bool KEEP>
+__device__ __forceinline__ void ground_body(GBody& gb, float ws, v3& v, v3& w, float& res) {
   static_assert(SRL_CG_WORDS == 28, "cg_request reads seven float4 per record");
-  const float ws = L.P->c.warmstart;
   const float4* rec = gb.rec;
-  v3 v, w;
   // The guards are nested: the points of a manifold are a prefix.
   static_assert(SRL_GMAXP == 4, "four nested guards below");
   if (!AHEAD) {
-    const float4 a0 = *(const float4*)gb.pvw;
-    const float2 a1 = *(const float2*)(gb.pvw + 4);
-    v = V(a0.x, a0.z, a1.x); w = V(a0.y, a0.w, a1.y);
+    if (!KEEP) {
+      const float4 a0 = *(const float4*)gb.pvw;
+      const float2 a1 = *(const float2*)(gb.pvw + 4);
+      v = V(a0.x, a0.z, a1.x); w = V(a0.y, a0.w, a1.y);
+    }
     ground_point<WARM>(cg_load(rec, 0), gb, 0, ws, v, w, res);        // (a body lane is called with np >= 1)
     if (gb.np > 1) {
       ground_point<WARM>(cg_load(rec, 1), gb, 1, ws, v, w, res);
@@ -759,12 +758,18 @@ __device__ __forceinline__ void ground_body(const Lds& L, GBody& gb, float& res)
   } else {
     const unsigned ra = (unsigned)(size_t)rec;   // the LDS byte address (the low word of the generic pointer)
     GRec r0, r1, r2, r3;
-    f4 a0; f2 a1;
-    float none = 0.0f;
-    cg_request_first((unsigned)(size_t)gb.pvw, ra, a0, a1, r0);
-    cg_request<1>(ra, r1, none);
-    cg_arrive_first(a0, a1, r0);
-    v = V(a0.x, a0.z, a1.x); w = V(a0.y, a0.w, a1.y);
+    if (!KEEP) {
+      f4 a0; f2 a1;
+      float none = 0.0f;
+      cg_request_first((unsigned)(size_t)gb.pvw, ra, a0, a1, r0);
+      cg_request<1>(ra, r1, none);
+      cg_arrive_first(a0, a1, r0);
+      v = V(a0.x, a0.z, a1.x); w = V(a0.y, a0.w, a1.y);
+    } else {
+      cg_request<0>(ra, r0, w.z);
+      cg_request<1>(ra, r1, w.z);
+      cg_arrive<7>(r0, w.z);
+    }
     ground_point<WARM>(r0, gb, 0, ws, v, w, res);
     cg_arrive<0>(r1, w.x);
     if (gb.np > 1) {
@@ -779,44 +784,7 @@ __device__ __forceinline__ void ground_body(const Lds& L, GBody& gb, float& res)
       }
     }
   }
-  *(float4*)gb.pvw = make_float4(v.x, w.x, v.y, w.y); *(float2*)(gb.pvw + 4) = make_float2(v.z, w.z);
-}
-
-// The same with the body's (v, w) kept in the caller's registers: sub-steps whose wave holds no pair point (half of all sub-steps, 20 -
-// 85 % of the slowest envs') run their sweeps as the ground phase alone, and nothing else reads or writes the velocities during the solve.
-template <bool WARM, bool AHEAD>
-__device__ __forceinline__ void ground_body_keep(const Lds& L, GBody& gb, v3& v, v3& w, float& res) {
-  const float ws = L.P->c.warmstart;
-  const float4* rec = gb.rec;
-  if (!AHEAD) {
-    ground_point<WARM>(cg_load(rec, 0), gb, 0, ws, v, w, res);
-    if (gb.np > 1) {
-      ground_point<WARM>(cg_load(rec, 1), gb, 1, ws, v, w, res);
-      if (gb.np > 2) {
-        ground_point<WARM>(cg_load(rec, 2), gb, 2, ws, v, w, res);
-        if (gb.np > 3) ground_point<WARM>(cg_load(rec, 3), gb, 3, ws, v, w, res);
-      }
-    }
-  } else {
-    const unsigned ra = (unsigned)(size_t)rec;
-    GRec r0, r1, r2, r3;
-    cg_request<0>(ra, r0, w.z);
-    cg_request<1>(ra, r1, w.z);
-    cg_arrive<7>(r0, w.z);
-    ground_point<WARM>(r0, gb, 0, ws, v, w, res);
-    cg_arrive<0>(r1, w.x);
-    if (gb.np > 1) {
-      cg_request<2>(ra, r2, w.z);
-      ground_point<WARM>(r1, gb, 1, ws, v, w, res);
-      cg_arrive<0>(r2, w.x);
-      if (gb.np > 2) {
-        cg_request<3>(ra, r3, w.z);
-        ground_point<WARM>(r2, gb, 2, ws, v, w, res);
-        cg_arrive<0>(r3, w.x);
-        if (gb.np > 3) ground_point<WARM>(r3, gb, 3, ws, v, w, res);
-      }
-    }
-  }
+  if (!KEEP) { *(float4*)gb.pvw = make_float4(v.x, w.x, v.y, w.y); *(float2*)(gb.pvw + 4) = make_float2(v.z, w.z); }
 }
 
 __device__ __forceinline__ Point make_pair_point(const Lds& L, int sl, int i) {
@@ -890,10 +858,12 @@ __device__ __forceinline__ void point_turn(const Lds& L, Point& p, float& res) {
 // lanes, and manifold slots are handed out lowest first), so the sweep is wave 0's alone: the phases follow each other in
 // program order — the LDS serves one wave's accesses in order — without a single block barrier, and the residual is a
 // ballot.  The other waves skip the sweeps and wait at the barrier that ends the solve.
-template <bool WARM, int PP, bool SOLO, bool GB, bool GA>
+template <bool WARM, int T, int PP, bool SOLO>
 __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb, Point (&pp)[PP], int ncol, int gslot,
                                              const int (&pslot)[PP], int gsweep, const unsigned long long (&cm)[2]) {
   // gslot / pslot: the turn a lane's point takes (ground: its index; colour phases: 4 * colour + index; -1: none)
+  typedef Variant<T, PP> VA;
+  static_assert(!SOLO || VA::SOLO, "a solo sweep in a variant that has none");
   float res = 0.0f;
   // A turn's guard is a SCALAR mask: a point's index in its manifold is its lane & 3 (four consecutive lanes per body / per slot), so
   // turn i of a phase is (the phase's lanes) & 0x1111... << i — `s_and_b64` + `s_and_saveexec_b64` on a uniform value
@@ -901,7 +871,7 @@ __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb
   // ≈ 75 cycles a turn (microbenchmark: compare -> VCC -> exec 32 cycles, a taken branch ≈ 32): the turns are unrolled, a
   // phase ends at its first empty turn (the points of a manifold are a prefix).
   constexpr unsigned long long T0 = 0x1111111111111111ull;
-  if (!GB) {     // the points of a body as turns of point lanes (round 1 - 4; kept for the variant that loses with body lanes)
+  if (!VA::GROUND_BODY) {     // the points of a body as turns of point lanes (round 1 - 4; kept for the variant that loses with body lanes)
     const unsigned long long gm = __ballot(gslot >= 0);
 #pragma unroll
     for (int i = 0; i < SRL_GMAXP; ++i) {
@@ -911,12 +881,12 @@ __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb
       __builtin_amdgcn_wave_barrier();
     }
   } else {
-    if (gb.np > 0) ground_body<WARM, !WARM && GA>(L, gb, res);
+    v3 v, w;
+    if (gb.np > 0) ground_body<WARM, !WARM && VA::GROUND_AHEAD, false>(gb, L.P->c.warmstart, v, w, res);
     __builtin_amdgcn_wave_barrier();
   }
   int c0 = 0;
-#ifndef SRL_NO_COLOUR_MASKS
-  if (SOLO && PP == 1) {   // the first two colours from masks made once per sub-step, straight-line (no ballot, no loop branch per colour)
+  if (SOLO) {   // the first two colours from masks made once per sub-step, straight-line (no ballot, no loop branch per colour)
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       if (c >= ncol) break;
@@ -930,7 +900,6 @@ __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb
     }
     c0 = 2;
   }
-#endif
 #pragma unroll 1
   for (int c = c0; c < ncol; ++c) {
     if (!SOLO) __syncthreads();
@@ -967,6 +936,7 @@ __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb
 
 template <int T, int PP>
 __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gsweep) {
+  typedef Variant<T, PP> VA;
   const DevParams& P = *L.P;
   // With two contact points per thread the register file is full: lane-dependent LDS addresses that the compiler
   // hoists out of the sub-step loop end up spilled to scratch and are reloaded from memory in every sub-step.  An
@@ -1055,7 +1025,7 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
   STAMP(3);
   // (5) narrowphase: G lanes per slot
   {
-    constexpr int G = SRL_GJK_GROUP(T, PP);
+    constexpr int G = VA::GJK_GROUP;
     const int gl = tid & (G - 1);
     for (int sl = tid / G; sl < P.NS; sl += T / G)
       if (L.POS()[sl] >= 0) narrowphase_slot<G>(L, sl, gl);
@@ -1081,20 +1051,7 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
     gb.pvw = L.VW(0); gb.rec = cg_rec(L, 0, 0);
 #pragma unroll
     for (int i = 0; i < SRL_GMAXP; ++i) { gb.acc[i][0] = 0.0f; gb.acc[i][1] = 0.0f; gb.acc[i][2] = 0.0f; }
-    // The ground phase by body lanes (ground_body) in every variant but the four-wave one with one point per thread (9 - 16
-    // rocks, small batches): built for three waves per SIMD (168 VGPRs) it spills 185 registers with it against 113 and loses
-    // 9 % (1,024 / 2,048 envs x 16 rocks); the others gain 3 - 5 % (profiles/r05_ground_body_ab.txt).  SRL_GROUND_TURNS: A / B.
-#ifdef SRL_GROUND_TURNS
-    constexpr bool GB = false;
-#else
-    constexpr bool GB = !(T == 256 && PP == 1);
-#endif
-    // the next ground point's record requested a point ahead (ground_body<AHEAD>): where the variant has the registers
-#ifndef SRL_GA_MASK
-#define SRL_GA_MASK 1
-#endif
-    constexpr bool GA = GB && ((T == 128 && PP == 1 && (SRL_GA_MASK & 1)) || (T == 128 && PP == 2 && (SRL_GA_MASK & 2)) ||
-                               (T == 256 && PP == 2 && (SRL_GA_MASK & 4)));
+    constexpr bool GB = VA::GROUND_BODY, GA = VA::GROUND_AHEAD;
     if (GB) {
     // the rows' constants of every ground point to LDS (over the world vertices, which nothing reads before the next
     // sub-step rewrites them), for the body lanes (tid < nb: wave 0)
@@ -1110,11 +1067,7 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
     __syncthreads();   // the records are in LDS
     }
     STAMP(5);
-#ifdef SRL_DIAG_NOSOLO
-    const bool solo = false;                           // diagnostic build: every sweep through the block-wide path
-#else
-    const bool solo = PP == 1 && misc[M_SOLO] != 0;   // (the variants with two points per thread are out of registers as it is)
-#endif
+    const bool solo = VA::SOLO && misc[M_SOLO] != 0;
     const int gslot = gp.valid ? gp.idx : -1;
     // the lanes of the first two colours (solo sweeps: solver_sweep)
     unsigned long long cm[2];
@@ -1130,32 +1083,28 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
         bool anyp = false;
 #pragma unroll
         for (int r = 0; r < PP; ++r) anyp |= pp[r].valid;
-#ifdef SRL_NO_GROUND_ONLY
-        const bool ground_only = false;
-#else
         const bool ground_only = GB && __ballot(anyp) == 0ull;   // (wave-uniform)
-#endif
-        if (ground_only) {   // no pair point: the sweeps are the ground phase, the velocities stay in registers (ground_body_keep)
+        if (ground_only) {   // no pair point: the sweeps are the ground phase, the velocities stay in registers (ground_body<KEEP>)
           v3 v = V(0.0f, 0.0f, 0.0f), w = V(0.0f, 0.0f, 0.0f);
           if (gb.np > 0) {
             const float4 a0 = *(const float4*)gb.pvw;
             const float2 a1 = *(const float2*)(gb.pvw + 4);
             v = V(a0.x, a0.z, a1.x); w = V(a0.y, a0.w, a1.y);
             float res = 0.0f;
-            ground_body_keep<true, false>(L, gb, v, w, res);
+            ground_body<true, false, true>(gb, P.c.warmstart, v, w, res);
           }
           for (int it = 0; it < P.c.solver_iterations; ++it) {
             done++;
             float res = 0.0f;
-            if (gb.np > 0) ground_body_keep<false, GA>(L, gb, v, w, res);
+            if (gb.np > 0) ground_body<false, GA, true>(gb, P.c.warmstart, v, w, res);
             if (__ballot(res * res > P.c.residual_threshold) == 0ull) break;
           }
           if (gb.np > 0) { *(float4*)gb.pvw = make_float4(v.x, w.x, v.y, w.y); *(float2*)(gb.pvw + 4) = make_float2(v.z, w.z); }
         } else {
-          solver_sweep<true, PP, PP == 1, GB, GA>(L, gp, gb, pp, ncol, gslot, pslot, 0, cm);
+          solver_sweep<true, T, PP, VA::SOLO>(L, gp, gb, pp, ncol, gslot, pslot, 0, cm);
           for (int it = 0; it < P.c.solver_iterations; ++it) {
             done++;
-            if (!solver_sweep<false, PP, PP == 1, GB, GA>(L, gp, gb, pp, ncol, gslot, pslot, 0, cm)) break;
+            if (!solver_sweep<false, T, PP, VA::SOLO>(L, gp, gb, pp, ncol, gslot, pslot, 0, cm)) break;
           }
         }
         if (tid == 0) misc[M_CNT] = done;   // (M_CNT is free between the calls of newest_contacts)
@@ -1163,10 +1112,10 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
       __syncthreads();
       gsweep += misc[M_CNT];
     } else {
-      solver_sweep<true, PP, false, GB, GA>(L, gp, gb, pp, ncol, gslot, pslot, 0, cm);
+      solver_sweep<true, T, PP, false>(L, gp, gb, pp, ncol, gslot, pslot, 0, cm);
       for (int it = 0; it < P.c.solver_iterations; ++it) {
         gsweep++;
-        if (!solver_sweep<false, PP, false, GB, GA>(L, gp, gb, pp, ncol, gslot, pslot, gsweep, cm)) break;
+        if (!solver_sweep<false, T, PP, false>(L, gp, gb, pp, ncol, gslot, pslot, gsweep, cm)) break;
       }
     }
 #ifdef SRL_STAMPS
@@ -1296,13 +1245,8 @@ __device__ __forceinline__ MeshHdr stage_mesh_hdr(const MeshHdr* __restrict__ mh
   return r;
 }
 
-#ifdef SRL_STAGE_TAIL_INLINE    // (A / B builds only)
-#define SRL_TAIL_ATTR __forceinline__
-#else
-#define SRL_TAIL_ATTR __attribute__((noinline))
-#endif
 template <int T>
-__device__ SRL_TAIL_ATTR void stage_tail(const DevParams* __restrict__ Pp, float4* __restrict__ stage, int e, int nb) {
+__device__ __attribute__((noinline)) void stage_tail(const DevParams* __restrict__ Pp, float4* __restrict__ stage, int e, int nb) {
   const DevParams& P = *Pp;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x;
@@ -1342,9 +1286,6 @@ __device__ __forceinline__ void step_body(const DevParams* __restrict__ Pp, cons
                                           int force_reset, const int32_t* __restrict__ order, float4* __restrict__ stage) {
   const DevParams& P = *Pp;
   extern __shared__ __attribute__((aligned(16))) float sm[];
-#ifdef SRL_STEP_PRIO
-  __builtin_amdgcn_s_setprio(SRL_STEP_PRIO);
-#endif
   // order (may be NULL): the env this workgroup serves — a permutation of the batch written by srl_k_order_* below, envs
   // with the longest expected settle first.  Envs are independent, so the results do not depend on it.
   const int e = order ? order[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;
@@ -1548,9 +1489,7 @@ __device__ __forceinline__ void step_body(const DevParams* __restrict__ Pp, cons
   }
 
   // ---- the rocks' render records (stage.h), by a function of its own: see stage_tail
-#ifndef SRL_NO_STAGE_TAIL
   if (stage != nullptr) stage_tail<T>(Pp, stage, e, nb);
-#endif
 }
 
 // Variants: T threads per env, one contact point of the body-body manifolds per thread (4 NS <= T; NS = 28 / 64 / 128
@@ -1560,6 +1499,24 @@ __device__ __forceinline__ void step_body(const DevParams* __restrict__ Pp, cons
 // The 16-rock variant is built for three waves per SIMD (168 VGPRs, 62 spilled to scratch): its shapes (2,048 - 4,096
 // envs x 16 rocks) are throughput-bound, and a third workgroup per CU is worth more than the spills cost — 60.7 -> 50.1 ms
 // per launch at 4,096 envs; four waves per SIMD (128 VGPRs) spill 108 registers and lose: 80 ms.
+// What a variant <T, PP> chooses besides its threads and points per thread, each with its measured reason (substep and
+// solver_sweep read these; the host's row of the variant is k_step_variants, stackrl_hip.hip):
+template <int T, int PP>
+struct Variant {
+  // lanes per manifold slot in the narrow phase: 32 in the 128-thread variant of <= 8 rocks, 16 where there are more slots than
+  // groups (round 5, same box: 1,024 x 16 +1.6 %, 4,096 x 16 +2 %, the headline shape indifferent; bit-identical either way)
+  static constexpr int GJK_GROUP = T == 128 && PP == 1 ? 32 : 16;
+  // the ground phase by body lanes (ground_body) in every variant but the four-wave one with one point per thread (9 - 16
+  // rocks, small batches): built for three waves per SIMD (168 VGPRs) it spills 185 registers with it against 113 and loses
+  // 9 % (1,024 / 2,048 envs x 16 rocks); the others gain 3 - 5 % (profiles/r05_ground_body_ab.txt)
+  static constexpr bool GROUND_BODY = !(T == 256 && PP == 1);
+  // the next ground point's record requested a point ahead (ground_body<AHEAD>): where the variant has the registers
+  static constexpr bool GROUND_AHEAD = T == 128 && PP == 1;
+  // sweeps by wave 0 alone while it holds every contact point (solver_sweep<SOLO>): the variants with two points per thread
+  // are out of registers as it is
+  static constexpr bool SOLO = PP == 1;
+};
+
 extern "C" __global__ void __launch_bounds__(128, 2) srl_k_step(const DevParams* __restrict__ Pp,
     const int64_t* __restrict__ action, int force_reset, const int32_t* __restrict__ order, float4* __restrict__ stage) {
   step_body<128, 1>(Pp, action, force_reset, order, stage);

@@ -34,6 +34,9 @@ int fail(int code, const char* fmt, const char* arg = "") {
 
 struct EventPair { hipEvent_t a, b; int which; };
 
+// the settle kernel's variants: <waves per env>W_PP<pair-manifold points per thread>; rows of k_step_variants below
+enum StepVariant { STEP_2W_PP1 = 0, STEP_4W_PP1, STEP_4W_PP2, STEP_2W_PP2, STEP_VARIANTS };
+
 }  // namespace
 
 struct srl_env {
@@ -52,8 +55,7 @@ struct srl_env {
   // allocated in srl_create, so that srl_reset allocates nothing and handles share no buffer
   float* d_reset_r = nullptr;
   uint8_t* d_reset_d = nullptr;
-  int step_threads = 256;
-  int step_pp = 1;
+  StepVariant step_variant = STEP_4W_PP1;   // chosen by srl_load_meshes
   int concurrent_envs = 0;   // srl_set_concurrent_envs: envs stepping on the device at the same time, over all handles
   // launch order of srl_k_step (settle.hip, srl_k_order_*): -1 = by batch size (on when the envs outnumber the resident
   // workgroups), 0 = index order, 1 = highest release first (srl_set_launch_order)
@@ -140,25 +142,35 @@ int derive(DevParams& P) {
 // caller that splits its batch over several handles says so with srl_set_concurrent_envs (`concurrent`, 0 = this handle
 // alone).  SRL_STEP_VARIANT=two_wave | four_wave overrides the choice (parity tests).
 bool two_wave_variant(const DevParams& P, int concurrent) {
-  const int L = P.c.episode_length;
-  if (L <= 8 || L > 16) return false;
   const char* v = getenv("SRL_STEP_VARIANT");
   if (v && !strcmp(v, "two_wave")) return true;
   if (v && !strcmp(v, "four_wave")) return false;
   return (concurrent > P.c.n_envs ? concurrent : P.c.n_envs) >= 3072;
 }
 
-// threads per env workgroup of the settle kernel (settle.hip "Variants"): 128 up to 8 rocks and for the two-wave variant of
-// 9 - 16 rocks, 256 otherwise
-int step_threads_of(const DevParams& P, int concurrent) {
-  const int NS = nslots(P.c.episode_length);
-  if (4 * NS <= 128 && SRL_GMAXP * P.c.episode_length <= 128) return 128;
-  if (two_wave_variant(P, concurrent)) return 128;
-  return 256;
+// The settle kernel's variants (settle.hip "Variants"), one row each.  `reports` is what srl_get_step_variant says of the
+// kernel; `lds_verts`: the env's LDS holds a copy of its bodies' local vertices (without it they are read from the L2-resident
+// mesh table: 70 instead of 97 KB per env above 16 rocks, so that two workgroups share a CU).
+typedef void (*step_kernel_t)(const DevParams*, const int64_t*, int, const int32_t*, float4*);
+struct StepRow { step_kernel_t kernel; int threads, pp, reports; bool lds_verts; };
+const StepRow k_step_variants[STEP_VARIANTS] = {
+    /* STEP_2W_PP1: up to 8 rocks          */ {srl_k_step, 128, 1, 0, true},
+    /* STEP_4W_PP1: 9 - 16 rocks           */ {srl_k_step_pp1, 256, 1, 1, true},
+    /* STEP_4W_PP2: above 16 rocks         */ {srl_k_step_pp2, 256, 2, 2, false},
+    /* STEP_2W_PP2: 9 - 16, large batches  */ {srl_k_step_t128, 128, 2, 3, false},
+};
+
+// one contact point of the pair manifolds per thread where the slots allow it (4 lanes per slot, SRL_GMAXP per body)
+StepVariant step_variant_of(const DevParams& P, int concurrent) {
+  const int L = P.c.episode_length, NS = nslots(L);
+  if (4 * NS <= 128 && SRL_GMAXP * L <= 128) return STEP_2W_PP1;
+  if (4 * NS > 256) return STEP_4W_PP2;
+  return two_wave_variant(P, concurrent) ? STEP_2W_PP2 : STEP_4W_PP1;
 }
 
 void layout(DevParams& P, int concurrent) {
   int L = P.c.episode_length;
+  const StepRow& sv = k_step_variants[step_variant_of(P, concurrent)];
   P.NS = nslots(L);
   P.NP = L * (L - 1) / 2 > 0 ? L * (L - 1) / 2 : 1;
   int o = 0;
@@ -184,13 +196,11 @@ void layout(DevParams& P, int concurrent) {
   P.S_BC = s; s += 8 * L;
   // (during the solve the region holds the ground points' row constants instead: SRL_GMAXP x SRL_CG_WORDS words per body)
   P.S_WV = s; s += (3 * P.VS > SRL_GMAXP * SRL_CG_WORDS ? 3 * P.VS : SRL_GMAXP * SRL_CG_WORDS) * L;
-  // above 16 rocks the local vertices are read from the (L2-resident) mesh table instead of an LDS copy: 70 instead of
-  // 97 KB per env, so that two workgroups share a CU
-  if (L > 16 || two_wave_variant(P, concurrent)) P.S_LV = -1; else { P.S_LV = s; s += 3 * P.VS * L; }
+  if (sv.lds_verts) { P.S_LV = s; s += 3 * P.VS * L; } else P.S_LV = -1;
   // the tail of the settle kernels stages the env's rocks for the render kernel (stage.h): one StageLds per wave, laid over
   // the scratch words above, which are dead by then — the words below (colouring scratch, misc, pair table) are not
   {
-    const int waves = step_threads_of(P, concurrent) / 64;
+    const int waves = sv.threads / 64;
     const int need = waves * (int)(sizeof(StageLds) / sizeof(float));
     if (s < need) s = need;
   }
@@ -259,18 +269,13 @@ int launch_step_render(srl_env* env, const int64_t* action, void* obs_map, void*
   }
   float4* stage = force_reset < 0 ? nullptr : env->d_stage;   // (sub-steps only: no render follows, the records go stale)
   if (force_reset < 0) env->stage_dirty = true;
-  if (env->step_pp == 0) SRL_LAUNCH(env, 0, srl_k_step, dim3(n), dim3(env->step_threads), env->step_lds, st, dP, action, force_reset, order, stage);
-  else if (env->step_pp == 2) SRL_LAUNCH(env, 0, srl_k_step_pp2, dim3(n), dim3(env->step_threads), env->step_lds, st, dP, action, force_reset, order, stage);
-  else if (env->step_pp == 3) SRL_LAUNCH(env, 0, srl_k_step_t128, dim3(n), dim3(env->step_threads), env->step_lds, st, dP, action, force_reset, order, stage);
-  else SRL_LAUNCH(env, 0, srl_k_step_pp1, dim3(n), dim3(env->step_threads), env->step_lds, st, dP, action, force_reset, order, stage);
+  const StepRow& sv = k_step_variants[env->step_variant];
+  SRL_LAUNCH(env, 0, sv.kernel, dim3(n), dim3(sv.threads), env->step_lds, st, dP, action, force_reset, order, stage);
   if (force_reset < 0) {   // srl_step_simulation: sub-steps only
     HIP_TRY(hipGetLastError());
     return SRL_OK;
   }
   const int L = P.c.episode_length;
-#ifdef SRL_NO_STAGE_TAIL     // (A / B builds only: round 4's path, the staging as a kernel of its own in every step)
-  env->stage_dirty = true;
-#endif
   if (env->stage_dirty) {   // a test hook moved bodies since the records were made: all of them again, by the kernel
     SRL_LAUNCH(env, 2, srl_k_stage, dim3(n, (L + 3) / 4), dim3(256), 0, st, P, env->d_stage, L, (const float*)nullptr,
                (const int32_t*)nullptr, (const int32_t*)nullptr);
@@ -493,25 +498,14 @@ int srl_load_meshes(srl_env* env, const float* verts, const int32_t* vert_off, c
   layout(P, env->concurrent_envs);
   if (P.BLOB != old_blob) return fail(SRL_EINVAL, "internal: blob layout changed");
   env->step_lds = sizeof(float) * (size_t)P.LDS_WORDS;
-  // experiment hook (tools / DESIGN.md section 8): SRL_STEP_LDS_PAD_KB pads the settle kernel's LDS request, i.e. lowers the
-  // number of env workgroups a CU holds, leaving LDS to kernels that run beside it
-  if (const char* pad = getenv("SRL_STEP_LDS_PAD_KB")) env->step_lds += (size_t)atoi(pad) * 1024;
   if (env->step_lds > 160 * 1024) return fail(SRL_EINVAL, "episode_length x mesh size exceeds the 160 KB LDS budget");
-  // threads per env / pair-manifold points per thread (settle.hip "Variants")
-  // 128 threads up to 8 rocks, 256 up to 16 (one contact point per thread), 256 with two points per thread above
-  // (settle.hip "Variants")
-  if (4 * P.NS <= 128 && SRL_GMAXP * P.c.episode_length <= 128) { env->step_threads = 128; env->step_pp = 0; }
-  else if (two_wave_variant(P, env->concurrent_envs)) { env->step_threads = 128; env->step_pp = 3; }
-  else if (4 * P.NS <= 256) { env->step_threads = 256; env->step_pp = 1; }
-  else { env->step_threads = 256; env->step_pp = 2; }
+  env->step_variant = step_variant_of(P, env->concurrent_envs);
   const int res = P.c.overhead_res;
   env->render_lds = render_lds_bytes(res);
   if (env->render_lds > 160 * 1024) return fail(SRL_EINVAL, "overhead_res exceeds the 160 KB LDS budget of the render tile (at most 176)");
   env->objmap_lds = 0;
-  HIP_TRY(hipFuncSetAttribute((const void*)srl_k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->step_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)srl_k_step_pp1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->step_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)srl_k_step_pp2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->step_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)srl_k_step_t128, hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->step_lds));
+  for (const StepRow& sv : k_step_variants)
+    HIP_TRY(hipFuncSetAttribute((const void*)sv.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->step_lds));
   HIP_TRY(hipFuncSetAttribute((const void*)srl_k_render, hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->render_lds));
   if (P.c.obs_dtype != SRL_DTYPE_UINT8)
     HIP_TRY(hipFuncSetAttribute((const void*)k_render_of_dtype[P.c.obs_dtype], hipFuncAttributeMaxDynamicSharedMemorySize, (int)env->render_lds));
@@ -534,9 +528,10 @@ int srl_set_concurrent_envs(srl_env* env, int32_t n_envs_on_device) {
 int srl_get_step_variant(srl_env* env, int32_t* threads, int32_t* points_per_thread, int32_t* kernel) {
   if (!env) return fail(SRL_EINVAL, "null env");
   if (!env->d_mh) return fail(SRL_ENOMESH, "srl_load_meshes must be called first (it chooses the variant)");
-  if (threads) *threads = env->step_threads;
-  if (points_per_thread) *points_per_thread = env->step_pp == 2 || env->step_pp == 3 ? 2 : 1;
-  if (kernel) *kernel = env->step_pp;
+  const StepRow& sv = k_step_variants[env->step_variant];
+  if (threads) *threads = sv.threads;
+  if (points_per_thread) *points_per_thread = sv.pp;
+  if (kernel) *kernel = sv.reports;
   return SRL_OK;
 }
 
