@@ -3,7 +3,7 @@
 Follows stackrl/baselines.py: `get_inputs` :21-26, `height` :28-43, `difference` :45-77, `corrcoef` :79-114,
 `correlate` :141-143, `goal_overlap` :152-156, `Baseline.call` :201-217.
 PINNED: checked against golden vectors produced by the reference's own baselines.py
-(tests/golden/make_baselines_golden.py -> baselines_golden.npz)."""
+(tests/golden/make_baselines_golden.py -> baselines_golden.npz, baselines_edges_golden.npz)."""
 import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
 
@@ -15,6 +15,13 @@ def get_inputs(inputs):
 
 def _windows(o, n):
   return sliding_window_view(o, n.shape)               # [OH, OW, h, w]
+
+
+def _window_sums(x):
+  """Sum of every window of x [OH, OW, h, w] in the order `np.sum` takes over one contiguous window (pairwise over its
+  h * w values).  On a flat window `corrcoef` divides rounding noise by rounding noise, so what it returns there
+  (exactly 0, or about 1e-16) depends on that order; with it the oracle returns the reference's own bits."""
+  return np.ascontiguousarray(x).reshape(x.shape[0], x.shape[1], -1).sum(axis=-1)
 
 
 def height(inputs):
@@ -49,9 +56,9 @@ def corrcoef(inputs, localized=False):
   f = np.zeros(W.shape[:2])
   if n_var == 0:
     return f
-  o_ = W - (np.where(nw, W, 0).sum(axis=(2, 3)) / cnt)[:, :, None, None]
-  o_var = np.where(nw, o_ ** 2, 0).sum(axis=(2, 3))
-  num = np.where(nw, n * o_, 0).sum(axis=(2, 3))
+  o_ = W - (_window_sums(np.where(nw, W, 0)) / cnt)[:, :, None, None]
+  o_var = _window_sums(np.where(nw, o_ ** 2, 0))
+  num = _window_sums(np.where(nw, n * o_, 0))
   ok = o_var != 0
   f[ok] = num[ok] / np.sqrt(n_var * o_var[ok])
   return f

@@ -33,7 +33,13 @@ def _stream(t):
 
 def heuristic_values(method, inputs, mask=True, difference_exponent=2, weights_exponent=2, localized=False,
                      threshold=0.75, generator=None):
-  """Value map float64 [B, OH, OW] of one method and (optionally) the goal-overlap mask bool [B, OH, OW]."""
+  """Value map float64 [B, OH, OW] of one method and (optionally) the goal-overlap mask bool [B, OH, OW].
+
+  An observation without a goal (its goal channel all zero) has `gmax = 0` (baselines.py:23): the reference divides by
+  zero there, and so does the device, without a check that would need a sync: that env's values are NaN / inf and its
+  action is arbitrary; the other envs of the batch are computed as ever.  An all-zero object map gives `height` 0 and a
+  mask that is True everywhere (`difference` and `correlate` divide by its zero sum: NaN, as in the reference).
+  A map too large to stage in one workgroup's LDS (H = 256 with h = 64) raises RuntimeError before anything is launched."""
   xm, xo = inputs
   for x in (xm, xo):
     if x.dtype != torch.uint8:    # the kernels read bytes (csrc/heuristics.hip)

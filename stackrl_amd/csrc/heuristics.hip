@@ -4,19 +4,24 @@
 // `goal_overlap` :152-156 and the selection of `Baseline.call` :201-217.  All of them are sliding-window reductions of
 // the (h x w) object map over the (H x W) height map — (H-h+1)(W-w+1) windows of h*w taps — which the reference runs
 // as double Python loops per observation.  Here: one 256-thread workgroup per env, the uint8 maps staged once in LDS
-// (16 KB + 1 KB), a 256-entry table k -> k / gmax so that every tap value is the same double numpy computes, one
-// thread per window (strided), float64 accumulation in row-major tap order.
+// (2 x 16 KB + 1 KB at 128 / 32; the host refuses a map that does not fit the device's LDS), a 256-entry table
+// k -> k / gmax so that every tap value is the same double numpy computes, one thread per window (strided), float64
+// accumulation in row-major tap order.  An env whose goal channel is all zero has gmax = 0 and, like the reference,
+// gets NaN / inf values; the other envs of the batch are not touched by it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/stackrl_qnet.h"
 
+__attribute__((visibility("hidden"))) void srl_qnet_set_error(const char* msg);   // qnet.hip: the text srl_qnet_last_error() returns (not exported)
+
 namespace {
-thread_local char h_err[256] = "";
-#define q_err h_err
+#define SET_ERR(...) do { char msg_[256]; snprintf(msg_, sizeof msg_, __VA_ARGS__); srl_qnet_set_error(msg_); } while (0)
 
-
+// LDS of one workgroup: the three byte maps, then (8-byte aligned: H*H and h*h may be odd) the doubles, then the ints.
+__host__ __device__ inline size_t lds_doubles_offset(int H, int h) { return (2 * (size_t)H * H + (size_t)h * h + 7) & ~(size_t)7; }
+inline size_t lds_bytes(int H, int h) { return lds_doubles_offset(H, h) + sizeof(double) * (256 + (size_t)h * h + 256) + sizeof(int) * 256; }
 
 enum { M_CORRELATE = 1, M_HEIGHT = 2, M_DIFFERENCE = 3, M_CORRCOEF = 4 };
 
@@ -36,7 +41,7 @@ k_heuristic(int method, const uint8_t* __restrict__ obs_map, const uint8_t* __re
   uint8_t* sm = lds;                    // [H*H] height channel
   uint8_t* sg = sm + H * H;             // [H*H] (height < goal) flags
   uint8_t* so = sg + H * H;             // [h*h] object map
-  double* lut = (double*)(so + ((h * h + 7) & ~7));   // [256] k / gmax
+  double* lut = (double*)(lds + lds_doubles_offset(H, h));   // [256] k / gmax
   double* wts = lut + 256;              // [h*h] difference weights / centred n for corrcoef
   double* red = wts + h * h;            // [256] reductions
   int* redi = (int*)(red + 256);        // [256]
@@ -243,28 +248,40 @@ int srl_heuristic(int32_t method, const uint8_t* obs_map, const uint8_t* obs_obj
                   int32_t B, int32_t H, int32_t h, int32_t difference_exponent, int32_t weights_exponent,
                   int32_t localized, double threshold, void* stream) {
   if (!obs_map || !obs_obj || !values || B < 1 || h < 1 || H < h || method < 1 || method > 4) {
-    snprintf(q_err, sizeof q_err, "srl_heuristic: bad arguments");
+    SET_ERR("srl_heuristic: bad arguments");
     return 1;
   }
-  size_t lds = 2 * (size_t)H * H + (((size_t)h * h + 7) & ~(size_t)7) + sizeof(double) * (256 + (size_t)h * h + 256) + sizeof(int) * 256;
-  hipFuncSetAttribute((const void*)k_heuristic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const size_t lds = lds_bytes(H, h);
+  int dev = 0, lds_max = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+  if (e != hipSuccess) { SET_ERR("srl_heuristic: %s", hipGetErrorString(e)); return 4; }
+  if (lds > (size_t)lds_max) {      // the whole map of one env is staged in LDS: nothing is launched when it cannot be
+    SET_ERR("srl_heuristic: H = %d, h = %d needs %zu bytes of LDS per workgroup, the device has %d", (int)H, (int)h, lds, lds_max);
+    return 1;
+  }
+  e = hipFuncSetAttribute((const void*)k_heuristic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) {
+    SET_ERR("srl_heuristic: H = %d, h = %d, %zu bytes of LDS: %s", (int)H, (int)h, lds, hipGetErrorString(e));
+    return 4;
+  }
   hipLaunchKernelGGL(k_heuristic, dim3(B), dim3(256), lds, (hipStream_t)stream, method, obs_map, obs_obj, values, mask,
                      H, h, difference_exponent, weights_exponent, localized, threshold);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(q_err, sizeof q_err, "srl_heuristic: %s", hipGetErrorString(e)); return 4; }
+  e = hipGetLastError();
+  if (e != hipSuccess) { SET_ERR("srl_heuristic: %s", hipGetErrorString(e)); return 4; }
   return 0;
 }
 
 int srl_baseline_select(const double* values, const uint8_t* mask, int32_t use_goal, int32_t minorder,
                         int64_t* actions, double* neg_values, int32_t B, int32_t OH, void* stream) {
   if (!values || !actions || (use_goal && !mask) || B < 1 || OH < 1 || minorder < 0) {
-    snprintf(q_err, sizeof q_err, "srl_baseline_select: bad arguments");
+    SET_ERR("srl_baseline_select: bad arguments");
     return 1;
   }
   hipLaunchKernelGGL(k_baseline_select, dim3(B), dim3(256), 0, (hipStream_t)stream, values, mask ? mask : (const uint8_t*)values,
                      use_goal, minorder, actions, neg_values, OH);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(q_err, sizeof q_err, "srl_baseline_select: %s", hipGetErrorString(e)); return 4; }
+  if (e != hipSuccess) { SET_ERR("srl_baseline_select: %s", hipGetErrorString(e)); return 4; }
   return 0;
 }
 

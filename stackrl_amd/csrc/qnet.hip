@@ -81,6 +81,9 @@ __global__ void __launch_bounds__(256) k_policy_head(const float* __restrict__ a
 }
 }  // namespace
 
+// for the other files of the library that report through srl_qnet_last_error (heuristics.hip); not part of the ABI
+__attribute__((visibility("hidden"))) void srl_qnet_set_error(const char* msg) { snprintf(q_err, sizeof q_err, "%s", msg); }
+
 extern "C" {
 
 const char* srl_qnet_last_error(void) { return q_err; }
