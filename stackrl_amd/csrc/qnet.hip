@@ -8,10 +8,13 @@
 //   in SGPRs as the FMA operand — no LDS traffic at all, 256 FMAs per 39 vector loads.
 //
 // policy head: one workgroup per env row; (value, index) arg-max with lowest-index ties, then epsilon-greedy select.
+// Boltzmann head: the same arg-max over adv / T + Gumbel noise made in registers from the sample's Philox stream
+//   (the definition: include/stackrl_explore.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 
+#include "../../include/stackrl_explore.h"
 #include "../../include/stackrl_qnet.h"
 
 namespace {
@@ -79,6 +82,53 @@ __global__ void __launch_bounds__(256) k_policy_head(const float* __restrict__ a
   }
   if (tid == 0) actions[b] = (u[b] > eps) ? (int64_t)si[0] : rnd[b];   // tf.where(uniform > e, argmax, random), dqn.py:336-348
 }
+
+// Philox4x32-10 of the counter (c0, 0, 0, 0) under the key (k0, k1)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t k0, uint32_t k1, uint32_t x[4]) {
+  uint32_t c1 = 0, c2 = 0, c3 = 0;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
+}
+
+__global__ void __launch_bounds__(256) k_boltzmann_head(const float* __restrict__ adv, const int64_t* __restrict__ keys,
+                                                        float temperature, int64_t* __restrict__ actions, int A) {
+  __shared__ float sv[256];
+  __shared__ int si[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* a = adv + (size_t)b * A;
+  const uint32_t k0 = (uint32_t)keys[2 * (size_t)b], k1 = (uint32_t)keys[2 * (size_t)b + 1];
+  float best = -3.0e38f; int bi = 0x7fffffff;      // a thread without a quad keeps this and loses to any index
+  const int quads = (A + 3) >> 2;
+  for (int j = tid; j < quads; j += 256) {
+    uint32_t x[4];
+    philox4x32_10((uint32_t)j, k0, k1, x);
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+      const int k = 4 * j + l;
+      if (k < A) {                                  // lanes of the last quad beyond A: neither read nor scored
+        const float u = ((float)(x[l] >> 9) + 0.5f) * 1.1920928955078125e-07f;       // 2^-23; exact
+        const float t = a[k] / temperature - logf(-logf(u));
+        if (t > best) { best = t; bi = k; }        // ascending k per thread: lowest index of its maxima
+      }
+    }
+  }
+  sv[tid] = best; si[tid] = bi;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if (tid < s) {
+      float ov = sv[tid + s]; int oi = si[tid + s];
+      if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) actions[b] = (int64_t)si[0];
+}
 }  // namespace
 
 // for the other files of the library that report through srl_qnet_last_error (heuristics.hip); not part of the ABI
@@ -123,6 +173,18 @@ int srl_policy_head(const float* adv, const float* u, const int64_t* rnd, float 
   hipLaunchKernelGGL(k_policy_head, dim3(B), dim3(256), 0, (hipStream_t)stream, adv, u, rnd, epsilon, actions, A);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { snprintf(q_err, sizeof q_err, "srl_policy_head: %s", hipGetErrorString(e)); return 4; }
+  return 0;
+}
+
+int srl_boltzmann_head(const float* adv, const int64_t* keys, float temperature, int64_t* actions, int32_t B, int32_t A,
+                       void* stream) {
+  if (!adv || !keys || !actions || B < 1 || A < 1 || !(temperature > 0.0f)) {
+    snprintf(q_err, sizeof q_err, "srl_boltzmann_head: bad arguments (pointers must be non-null, B >= 1, A >= 1, temperature > 0)");
+    return 1;
+  }
+  hipLaunchKernelGGL(k_boltzmann_head, dim3(B), dim3(256), 0, (hipStream_t)stream, adv, keys, temperature, actions, A);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { snprintf(q_err, sizeof q_err, "srl_boltzmann_head: %s", hipGetErrorString(e)); return 4; }
   return 0;
 }
 

@@ -36,6 +36,35 @@ class PolynomialDecay(object):
 EXPLORATION_MODES = ['epsilon-greedy', 'boltzmann']     # dqn.py:23-28
 
 
+def philox4x32_10(counter, key):
+  """Philox4x32-10: counter int64 [..., 4], key int64 [..., 2] (32-bit words in int64 elements, broadcast against each
+  other) -> int64 [..., 4].  The product of two 32-bit words wraps in int64; its low and high words are read by mask and
+  shift.  Pure torch, either device."""
+  c0, c1, c2, c3 = (counter[..., i] & 0xffffffff for i in range(4))
+  k0, k1 = key[..., 0] & 0xffffffff, key[..., 1] & 0xffffffff
+  for _ in range(10):
+    p0, p1 = c0 * 0xD2511F53, c2 * 0xCD9E8D57
+    c0, c1, c2, c3 = ((p1 >> 32) & 0xffffffff) ^ c1 ^ k0, p1 & 0xffffffff, ((p0 >> 32) & 0xffffffff) ^ c3 ^ k1, p0 & 0xffffffff
+    k0, k1 = (k0 + 0x9E3779B9) & 0xffffffff, (k1 + 0xBB67AE85) & 0xffffffff
+  return torch.stack((c0, c1, c2, c3), dim=-1)
+
+
+def boltzmann_uniform(x, dtype=torch.float32):
+  """The uniform number of a 32-bit Philox word: ((x >> 9) + 0.5) * 2^-23, exact in float32, within [2^-24, 1 - 2^-24]."""
+  return ((x >> 9).to(dtype) + 0.5) * 2.0 ** -23
+
+
+def boltzmann_noise(keys, A, dtype=torch.float32):
+  """The Gumbel noise z [B, A] of the Boltzmann head for the stream keys [B, 2] (int64; one per sample), by the definition
+  in include/stackrl_explore.h, which the kernel `k_boltzmann_head` computes in registers: action a of sample b takes
+  word a % 4 of Philox4x32-10(counter (a // 4, 0, 0, 0), key keys[b]).  Pure torch, either device."""
+  quads = (int(A) + 3) // 4
+  counter = torch.zeros((1, quads, 4), dtype=torch.int64, device=keys.device)
+  counter[0, :, 0] = torch.arange(quads, dtype=torch.int64, device=keys.device)
+  x = philox4x32_10(counter, keys[:, None, :]).reshape(keys.shape[0], 4 * quads)[:, :int(A)]
+  return -torch.log(-torch.log(boltzmann_uniform(x, dtype)))
+
+
 class KerasAdam(object):
   """`keras.optimizers.Adam` as the reference applies it (dqn.py:473; config.gin:90-93) over ONE flat fp32 bucket:
   m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); p -= lr_t m / (sqrt(v) + eps), lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)
@@ -302,10 +331,11 @@ class DQN(object):
   def policy_draws(self, batch_size):
     """The random numbers one exploring `policy` call over `batch_size` samples consumes, drawn as that call draws them.
     A policy evaluated group by group (`PipelinedVecStackEnv.collect_step`) hands each group its slice (`draws=`) and
-    takes the actions one call over the whole batch would take."""
-    if self._exploration_mode != 'epsilon-greedy':
-      raise NotImplementedError('group-wise collection is implemented for epsilon-greedy exploration')
+    takes the actions one call over the whole batch would take.  Every element of the tuple is indexed by sample:
+    epsilon-greedy draws (u, random action), Boltzmann one Philox stream key per sample, (keys [B, 2],) (`boltzmann_noise`)."""
     dev = next(self._q_net.parameters()).device
+    if self._exploration_mode == 'boltzmann':
+      return (torch.randint(0, 2 ** 32, (batch_size, 2), dtype=torch.int64, generator=self._gen, device=dev),)
     u = torch.rand(batch_size, generator=self._gen, device=dev)
     return u, torch.randint(self._n_actions, (batch_size,), generator=self._gen, device=dev)
 
@@ -321,10 +351,9 @@ class DQN(object):
         timer.stop()
 
   def _policy(self, inputs, exploration, values, draws):
-    if self._policy_op is not None and exploration and not values and self._exploration_mode == 'epsilon-greedy':
-      if draws is None:
-        return self._policy_op(self._q_net, inputs, self.exploration, self._gen)
-      return self._policy_op(self._q_net, inputs, self.exploration, self._gen, draws=draws)
+    if self._policy_op is not None and exploration and not values:
+      # epsilon or, in Boltzmann mode, the temperature
+      return self._policy_op(self._q_net, inputs, self.exploration, self._gen, draws=draws, mode=self._exploration_mode)
     with torch.no_grad():
       q = self._q_net(inputs)
     greedy = torch.argmax(q, dim=-1)                 # ties -> lowest index
@@ -333,6 +362,8 @@ class DQN(object):
       if self._exploration_mode == 'epsilon-greedy':
         u, rnd = draws if draws is not None else self.policy_draws(q.shape[0])
         actions = torch.where(u > e, greedy, rnd)
+      elif draws is not None:                        # per-sample streams: any partition of the batch takes the same actions
+        actions = torch.argmax(q / e + boltzmann_noise(draws[0], q.shape[-1], q.dtype), dim=-1)
       else:
         z = -torch.log(-torch.log(torch.rand(q.shape, generator=self._gen, device=q.device)))
         actions = torch.argmax(q / e + z, dim=-1)

@@ -1,4 +1,4 @@
-"""Python side of libstackrl_qnet.so (include/stackrl_qnet.h): the hand-written ops of the Q-net rollout path.
+"""Python side of libstackrl_qnet.so (include/stackrl_qnet.h, include/stackrl_explore.h): the hand-written ops of the Q-net rollout path.
 No CPU fallback: these functions need a HIP device and the built library."""
 import ctypes
 import os
@@ -80,6 +80,8 @@ def load():
     L.srl_conv3x3_relu_project.argtypes = [VP, VP, VP, VP, ctypes.c_float, VP] + [ctypes.c_int32] * 5 + [VP]
     L.srl_policy_head.restype = ctypes.c_int
     L.srl_policy_head.argtypes = [VP, VP, VP, ctypes.c_float, VP, ctypes.c_int32, ctypes.c_int32, VP]
+    L.srl_boltzmann_head.restype = ctypes.c_int
+    L.srl_boltzmann_head.argtypes = [VP, VP, ctypes.c_float, VP, ctypes.c_int32, ctypes.c_int32, VP]
     L.srl_qnet_last_error.restype = ctypes.c_char_p
     I32, I64, F = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
     L.srl_td_epilogue.restype = ctypes.c_int
@@ -222,6 +224,24 @@ def policy_head(adv, u, rnd, epsilon):
   with torch.cuda.device(adv.device):
     rc = load().srl_policy_head(adv.data_ptr(), u.contiguous().data_ptr(), rnd.contiguous().data_ptr(),
                                 float(epsilon), actions.data_ptr(), B, A, _stream(adv))
+  if rc:
+    raise RuntimeError(load().srl_qnet_last_error().decode())
+  return actions
+
+
+def boltzmann_head(adv, keys, temperature):
+  """Boltzmann head (dqn.py:349-358; the noise definition: include/stackrl_explore.h): adv [B,A] f32, keys [B,2] i64 (one
+  Philox stream key per sample, two 32-bit words) -> actions [B] i64."""
+  if not adv.is_cuda:
+    raise RuntimeError('boltzmann_head needs a HIP device (no CPU fallback)')
+  adv = adv.contiguous().float()
+  B, A = adv.shape
+  if keys.dtype != torch.int64 or tuple(keys.shape) != (B, 2) or keys.device != adv.device:
+    raise ValueError('keys must be an int64 [{}, 2] tensor on {}'.format(B, adv.device))
+  actions = torch.empty(B, dtype=torch.int64, device=adv.device)
+  with torch.cuda.device(adv.device):
+    rc = load().srl_boltzmann_head(adv.data_ptr(), keys.contiguous().data_ptr(), float(temperature), actions.data_ptr(),
+                                   B, A, _stream(adv))
   if rc:
     raise RuntimeError(load().srl_qnet_last_error().decode())
   return actions
@@ -801,7 +821,9 @@ class FastFeatures(object):
 class FusedPolicy(object):
   """Rollout policy (`DQN.collect` -> `policy(exploration=True)`, dqn.py:391-395) with the hand-written head:
   library convs for the two U-Nets and the position convs, HIP cross-correlation, HIP arg-max + epsilon-greedy.
-  Draws the same random numbers in the same order as `DQN.policy`, so both paths give identical actions."""
+  Draws the same random numbers in the same order as `DQN.policy`, so both paths give identical actions.
+  With mode='boltzmann' the head is `boltzmann_head`: the third argument of a call is the temperature and the draws are
+  one Philox stream key per sample (include/stackrl_explore.h)."""
 
   def __init__(self, chunk=2048, autocast=None, fast=None):
     # rollout batches are processed in chunks to bound activation memory: 2,048 samples hold ~10 GB of fp32 activations
@@ -813,17 +835,26 @@ class FusedPolicy(object):
     self._ff = None
 
   @staticmethod
-  def draws(net, B, gen, device):
+  def draws(net, B, gen, device, mode='epsilon-greedy'):
     """The random numbers one call over B samples consumes, drawn as that call draws them (`draws=` of `__call__`: a
     policy evaluated group by group passes each group its slice and takes the actions of one call over the batch)."""
+    if mode == 'boltzmann':
+      return (torch.randint(0, 2 ** 32, (B, 2), dtype=torch.int64, generator=gen, device=device),)
     u = torch.rand(B, generator=gen, device=device)
     return u, torch.randint(net.n_actions, (B,), generator=gen, device=device)
 
   @torch.no_grad()
-  def __call__(self, net, inputs, epsilon, gen, draws=None):
+  def __call__(self, net, inputs, epsilon, gen, draws=None, mode='epsilon-greedy'):
+    if mode not in ('epsilon-greedy', 'boltzmann'):
+      raise ValueError("Invalid value {} for argument mode. Must be 'epsilon-greedy' or 'boltzmann'.".format(mode))
     xm, xo = inputs
     B = xm.shape[0]
-    u, rnd = draws if draws is not None else self.draws(net, B, gen, xm.device)
+    if draws is None:
+      draws = self.draws(net, B, gen, xm.device, mode)
+    if mode == 'boltzmann':
+      keys, = draws
+    else:
+      u, rnd = draws
     out = torch.empty(B, dtype=torch.int64, device=xm.device)
     for s in range(0, B, self.chunk):
       e = min(B, s + self.chunk)
@@ -838,7 +869,7 @@ class FusedPolicy(object):
         x, _, w = net.features((xm[s:e], xo[s:e]))
       corr = xcorr_forward(x, w)
       adv = self._ff.pos(corr) if self.fast else net.pos(corr).flatten(1)
-      out[s:e] = policy_head(adv, u[s:e], rnd[s:e], epsilon)
+      out[s:e] = boltzmann_head(adv, keys[s:e], epsilon) if mode == 'boltzmann' else policy_head(adv, u[s:e], rnd[s:e], epsilon)
     return out
 
 
