@@ -901,7 +901,10 @@ def test_update_stays_finite_under_the_concurrent_env_step():
 
 
 _GEMM_LAYERS = [(32, 64, 32), (64, 64, 32), (128, 64, 32), (64, 128, 16), (128, 128, 16), (256, 128, 16), (128, 256, 8), (256, 256, 8),
-                (32, 64, 8), (64, 64, 16), (128, 64, 16), (256, 128, 8), (128, 256, 4)]
+                (32, 64, 8), (64, 64, 16), (128, 64, 16), (256, 128, 8), (128, 256, 4),
+                # the right U-Net's second bottom layer at 128 / 32, and the left U-Net's own layers at 64 x 64 observations
+                (64, 64, 8), (32, 64, 16), (64, 128, 8), (128, 128, 8), (256, 256, 4)]
+_GEMM_BATCH = 8     # (one workgroup for the layers whose workgroups take eight maps: test_rollout_forward_gpu.py runs every layer past it)
 
 
 @pytest.mark.parametrize('cin,cout,W', _GEMM_LAYERS)
@@ -912,7 +915,7 @@ def test_conv3x3_gemm_matches_torch_fp64(cin, cout, W, f32):
   plain output and a channel slice of a wider buffer."""
   from stackrl_amd import qops
   g = torch.Generator(device='cuda').manual_seed(cin + cout + W)
-  B = 8
+  B = _GEMM_BATCH
   dt = torch.float32 if f32 else torch.bfloat16
   x = torch.randn(B, cin, W, W, generator=g, device='cuda').to(dt).contiguous(memory_format=torch.channels_last)
   w = torch.randn(cout, cin, 3, 3, generator=g, device='cuda') / (3 * cin ** 0.5)
