@@ -66,7 +66,9 @@ __global__ void __launch_bounds__(256) k_policy_head(const float* __restrict__ a
   __shared__ int si[256];
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* a = adv + (size_t)b * A;
-  float best = -3.0e38f; int bi = 0x7fffffff;
+  // start: -inf at the thread's own first index — a pair that wins only what it may (a row of nothing but -inf or NaN
+  // resolves to index 0); a thread without an entry holds an index that loses to every real one
+  float best = -INFINITY; int bi = tid < A ? tid : 0x7fffffff;
   for (int k = tid; k < A; k += 256) {
     float t = a[k];
     if (t > best) { best = t; bi = k; }          // ascending k per thread: lowest index of its maxima
@@ -103,7 +105,9 @@ __global__ void __launch_bounds__(256) k_boltzmann_head(const float* __restrict_
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* a = adv + (size_t)b * A;
   const uint32_t k0 = (uint32_t)keys[2 * (size_t)b], k1 = (uint32_t)keys[2 * (size_t)b + 1];
-  float best = -3.0e38f; int bi = 0x7fffffff;      // a thread without a quad keeps this and loses to any index
+  // -inf at the thread's first index (a row of nothing but -inf resolves to index 0); a thread without a quad keeps an index
+  // that loses to any real one
+  float best = -INFINITY; int bi = 4 * tid < A ? 4 * tid : 0x7fffffff;
   const int quads = (A + 3) >> 2;
   for (int j = tid; j < quads; j += 256) {
     uint32_t x[4];
