@@ -36,6 +36,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "../../include/stackrl_greedy.h"
 #include "../../include/stackrl_qnet.h"
 #include "srl_bf16.h"
 
@@ -836,6 +837,21 @@ int srl_xcorr_mfma(int32_t mode, int32_t precision, const void* in, int32_t in_f
   if (mode == 0) return launch<64, 16, 4, 4, true, true, true>(in, in_f32, kern, kern_f32, precision, out, scratch, B, C, st);
   if (mode == 1) return launch<79, 16, 4, 4, false, true, false>(in, in_f32, kern, kern_f32, precision, out, scratch, B, C, st);
   return launch<64, 49, 1, 1, true, false, false>(in, in_f32, kern, kern_f32, precision, out, scratch, B, C, st);
+}
+
+// include/stackrl_greedy.h: the row-product forward at ANY batch size — one workgroup per sample and no channel split, so a
+// sample's map does not depend on the batch it is evaluated in (srl_xcorr_mfma picks the kernel and the split by B)
+int srl_xcorr_rows(int32_t precision, const void* in, const void* kern, int32_t f32, float* out, int32_t B, int32_t C, int32_t H,
+                   int32_t kh, void* stream) {
+  if (!in || !kern || !out || B < 1 || C < 1 || C > 16 || H != 128 || kh != 32 || precision < 0 || precision > 1 ||
+      (precision == 1 && !f32)) {
+    snprintf(x_err, sizeof x_err, "srl_xcorr_rows: bad arguments (128 / 32 maps of at most 16 channels; bf16x3 needs float32 operands)");
+    return 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (precision == 1) return launch_rows<true, true>(in, kern, out, B, C, st);
+  if (f32) return launch_rows<false, true>(in, kern, out, B, C, st);
+  return launch_rows<false, false>(in, kern, out, B, C, st);
 }
 
 }  // extern "C"

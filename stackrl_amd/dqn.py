@@ -65,6 +65,35 @@ def boltzmann_noise(keys, A, dtype=torch.float32):
   return -torch.log(-torch.log(boltzmann_uniform(x, dtype)))
 
 
+def greedy_head_reference(adv, v, n_valid=None):
+  """The greedy head by the definition in include/stackrl_greedy.h, which the kernel `k_greedy_head` computes in one pass per
+  env: adv [B, A] or [B, G, A] float32 (G rows per env, the first `n_valid` valid; None = all), v [B] float32 or None (not
+  dueling: q = adv) -> (actions [B] int64, the flat index r * A + p with ties to the lowest; stats [B, 4] float64 {max q, min q,
+  sum q, sum q^2} over the valid rows; q float32 in the shape of adv, rows beyond n_valid -inf).  Pure torch, either device."""
+  flat2 = adv.dim() == 2
+  a = (adv[:, None] if flat2 else adv).float()
+  B, G, A = a.shape
+  n_valid = G if n_valid is None else int(n_valid)
+  if not 1 <= n_valid <= G:
+    raise ValueError('n_valid must be in 1..{}, got {}'.format(G, n_valid))
+  a = a[:, :n_valid]
+  if v is None:
+    qv = a
+  else:
+    m = (a.double().sum(dim=-1, keepdim=True) / A).float()           # float64 sum, one rounding to float32
+    qv = (a - m) + v.reshape(B, 1, 1).float()                        # models.py:188-192, in this order
+  flat = qv.reshape(B, n_valid * A)
+  nan = torch.isnan(flat)
+  top = torch.where(nan, torch.full_like(flat, -float('inf')), flat)  # a NaN never wins; nothing but NaN / -inf: index 0
+  actions = torch.argmax(top, dim=-1)
+  d = flat.double()
+  stats = torch.stack((top.amax(dim=-1).double(), torch.where(nan, torch.full_like(flat, float('inf')), flat).amin(dim=-1).double(),
+                       d.sum(dim=-1), (d * d).sum(dim=-1)), dim=-1)
+  q = torch.full((B, G, A), -float('inf'), dtype=torch.float32, device=adv.device)
+  q[:, :n_valid] = qv
+  return actions, stats, (q[:, 0] if flat2 else q)
+
+
 class KerasAdam(object):
   """`keras.optimizers.Adam` as the reference applies it (dqn.py:473; config.gin:90-93) over ONE flat fp32 bucket:
   m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); p -= lr_t m / (sqrt(v) + eps), lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)
@@ -370,6 +399,43 @@ class DQN(object):
     else:
       actions = greedy
     return (actions, q) if values else actions
+
+  @torch.no_grad()
+  def greedy(self, inputs, stats=False, values=False, n_valid=None):
+    """Greedy acting by the definition of include/stackrl_greedy.h (`greedy_head_reference`): actions [B], then as asked
+    stats [B, 4] float64 {max, min, sum, sum of squares of Q(s, .)} and Q [B, G * A].  inputs[1] may be the Stack-v2 layout
+    [B, G, h, w, 1] (G object maps per env, the first `n_valid` valid; the action is row * A + pixel).  With a `policy_op`
+    that has `.greedy` (qops.FusedPolicy) the rollout kernels run and no Q tensor exists unless `values` asks for it;
+    otherwise the module's own pieces followed by the definition in torch (any device)."""
+    timer = self.policy_timer
+    if timer is not None:
+      timer.start()
+    try:
+      if hasattr(self._policy_op, 'greedy'):
+        return self._policy_op.greedy(self._q_net, inputs, n_valid=n_valid, stats=stats, values=values)
+      a, st, q = self._greedy_module(inputs, n_valid)
+      out = (a,) + ((st,) if stats else ()) + ((q.reshape(q.shape[0], -1),) if values else ())
+      return out if len(out) > 1 else a
+    finally:
+      if timer is not None:
+        timer.stop()
+
+  def _greedy_module(self, inputs, n_valid):
+    net = self._q_net
+    xm, xo = inputs
+    B = xm.shape[0]
+    G = xo.shape[1] if xo.dim() == 5 else 1
+    if xo.dim() == 5:      # the reference's layout (env.py:472-480): the overhead map once per object map
+      inputs = (xm[:, None].expand(B, G, *xm.shape[1:]).reshape(B * G, *xm.shape[1:]), xo.reshape(B * G, *xo.shape[2:]))
+    if not all(hasattr(net, k) for k in ('features', 'correlation', '_pos')):
+      return greedy_head_reference(net(inputs).reshape(B, G, -1), None, n_valid)     # an opaque module: Q is what it returns
+    x, x0, w = net.features(inputs)
+    adv = net._pos(net.correlation(x, w)).flatten(1).reshape(B, G, -1)
+    v = None
+    if getattr(net, 'dueling', False):
+      x0 = x0.reshape(B, G, *x0.shape[1:])[:, 0]
+      v = net.value(x0.mean(dim=(2, 3)) if net.dueling_avg_pool else x0.amax(dim=(2, 3))).reshape(B)
+    return greedy_head_reference(adv, v, n_valid)
 
   def acknowledge_reset(self):
     self._replay_memory.set_terminal()               # dqn.py:381-385

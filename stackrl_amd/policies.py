@@ -56,3 +56,19 @@ class OrientationGreedy(object):
     values = values.reshape(B, -1)                                          # [B, n * A]
     actions = torch.argmin(values, dim=-1) if self.minimize else torch.argmax(values, dim=-1)
     return (actions, values) if self.value else actions
+
+
+class FusedOrientationGreedy(object):
+  """`OrientationGreedy` on the agent's greedy path (`DQN.greedy`; with `policy_op=qops.FusedPolicy` the rollout kernels and
+  the head of include/stackrl_greedy.h): the observation stays in the vectorised env's layout, so the left U-Net and the
+  state value run once per env instead of once per orientation, and no [B, n * A] value tensor exists unless `value=True`
+  asks for it.  Same call signature and the same action `orientation * A + pixel`."""
+
+  def __init__(self, agent, value=False):
+    if not callable(getattr(agent, 'greedy', None)):
+      raise TypeError('agent must have a greedy method.')
+    self.agent, self.value = agent, value
+
+  @torch.no_grad()
+  def __call__(self, inputs, n_valid=None):
+    return self.agent.greedy(inputs, values=self.value, n_valid=n_valid)

@@ -1,4 +1,4 @@
-"""Python side of libstackrl_qnet.so (include/stackrl_qnet.h, include/stackrl_explore.h): the hand-written ops of the Q-net rollout path.
+"""Python side of libstackrl_qnet.so (include/stackrl_qnet.h, include/stackrl_explore.h, include/stackrl_greedy.h): the hand-written ops of the Q-net rollout path.
 No CPU fallback: these functions need a HIP device and the built library."""
 import ctypes
 import os
@@ -82,6 +82,13 @@ def load():
     L.srl_policy_head.argtypes = [VP, VP, VP, ctypes.c_float, VP, ctypes.c_int32, ctypes.c_int32, VP]
     L.srl_boltzmann_head.restype = ctypes.c_int
     L.srl_boltzmann_head.argtypes = [VP, VP, ctypes.c_float, VP, ctypes.c_int32, ctypes.c_int32, VP]
+    L.srl_xcorr_rows.restype = ctypes.c_int
+    L.srl_xcorr_rows.argtypes = [ctypes.c_int32, VP, VP, ctypes.c_int32, VP] + [ctypes.c_int32] * 4 + [VP]
+    L.srl_greedy_head.restype = ctypes.c_int
+    L.srl_greedy_head.argtypes = [VP, VP] + [ctypes.c_int32] * 4 + [VP, VP, VP, VP]
+    L.srl_tvalue_fwd.restype = ctypes.c_int
+    L.srl_tvalue_fwd.argtypes = [VP] * 8 + [ctypes.c_int32] * 4 + [VP]
+    L.srl_train_conv_last_error.restype = ctypes.c_char_p
     L.srl_qnet_last_error.restype = ctypes.c_char_p
     I32, I64, F = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
     L.srl_td_epilogue.restype = ctypes.c_int
@@ -216,6 +223,24 @@ def xcorr_forward(x, w, precision=None):
   return out
 
 
+def xcorr_forward_rows(x, w):
+  """`xcorr_forward` for greedy acting: where the row-product kernel is built (128 / 32 maps of at most 16 channels, both
+  operands float32 — hi / lo split — or both bfloat16) it runs at any batch size (include/stackrl_greedy.h srl_xcorr_rows), so
+  a sample's map does not depend on the batch it is evaluated in; other shapes take `xcorr_forward`."""
+  if not (x.is_cuda and x.dim() == 4 and tuple(x.shape[-2:]) == (128, 128) and tuple(w.shape[-2:]) == (32, 32) and x.shape[1] <= 16 and
+          x.dtype == w.dtype and x.dtype in (torch.float32, torch.bfloat16)):
+    return xcorr_forward(x, w)
+  x = x.contiguous(); w = w.contiguous()
+  B, C = x.shape[:2]
+  f32 = int(x.dtype == torch.float32)
+  out = torch.empty((B, 1, 97, 97), dtype=torch.float32, device=x.device)
+  with torch.cuda.device(x.device):
+    rc = load().srl_xcorr_rows(BF16X3 if f32 else BF16, x.data_ptr(), w.data_ptr(), f32, out.data_ptr(), B, C, 128, 32, _stream(x))
+  if rc:
+    raise RuntimeError(load().srl_xcorr_mfma_last_error().decode())
+  return out
+
+
 def policy_head(adv, u, rnd, epsilon):
   """Epsilon-greedy head (dqn.py:334-348): adv [B,A] f32, u [B] f32, rnd [B] i64 -> actions [B] i64."""
   adv = adv.contiguous().float()
@@ -245,6 +270,32 @@ def boltzmann_head(adv, keys, temperature):
   if rc:
     raise RuntimeError(load().srl_qnet_last_error().decode())
   return actions
+
+
+def greedy_head(adv, v=None, n_valid=None, stats=False, values=False):
+  """Greedy head (the definition: include/stackrl_greedy.h): adv [B,A] or [B,G,A] f32 (G rows per env, the first `n_valid`
+  valid; None = all), v [B] f32 or None (not dueling: q = adv) -> actions [B] i64 (the flat index r * A + p), then, as asked,
+  stats [B,4] f64 {max q, min q, sum q, sum q^2} and q (float32, the shape of adv; rows beyond n_valid are -inf)."""
+  if not adv.is_cuda:
+    raise RuntimeError('greedy_head needs a HIP device (no CPU fallback)')
+  if adv.dim() not in (2, 3):
+    raise ValueError('greedy_head: adv must be [B, A] or [B, G, A], got {}'.format(tuple(adv.shape)))
+  adv = adv.contiguous().float()
+  B, G, A = (adv.shape[0], 1, adv.shape[1]) if adv.dim() == 2 else adv.shape
+  if v is not None:
+    if v.numel() != B or v.device != adv.device:
+      raise ValueError('greedy_head (srl_greedy_head): v must hold {} values on {}, got {} on {}'.format(B, adv.device, tuple(v.shape), v.device))
+    v = v.reshape(B).contiguous().float()
+  n_valid = G if n_valid is None else int(n_valid)
+  actions = torch.empty(B, dtype=torch.int64, device=adv.device)
+  st = torch.empty((B, 4), dtype=torch.float64, device=adv.device) if stats else None
+  q = torch.empty_like(adv) if values else None
+  with torch.cuda.device(adv.device):
+    rc = load().srl_greedy_head(adv.data_ptr(), _ptr(v), B, G, n_valid, A, actions.data_ptr(), _ptr(st), _ptr(q), _stream(adv))
+  if rc:
+    raise RuntimeError(load().srl_qnet_last_error().decode())
+  out = (actions,) + ((st,) if stats else ()) + ((q,) if values else ())
+  return out if len(out) > 1 else actions
 
 
 _CL = torch.channels_last
@@ -709,8 +760,9 @@ class FastFeatures(object):
     w, b = self._w[m]
     return _cl(torch.nn.functional.conv2d(x, w, None, padding=m.padding)), b
 
-  def _unet(self, U, obs):
-    """obs: the env's uint8 observation [B,H,W,c] (channels-last memory)."""
+  def _unet(self, U, obs, bottom=False):
+    """obs: the env's uint8 observation [B,H,W,c] (channels-last memory).  bottom: also return the bottleneck (the output of
+    the bottom block), channels-last."""
     F = torch.nn.functional
     B = obs.shape[0]
     cats = []
@@ -754,6 +806,7 @@ class FastFeatures(object):
       else:
         y, b = self._conv(m, x)
         x = bias_act(y, b)
+    x0 = x
     n = len(U.up)
     for k, (up, blk) in enumerate(zip(U.up, U.upconv)):
       cat = cats.pop()
@@ -785,13 +838,22 @@ class FastFeatures(object):
       else:
         y, b = self._conv(blk[2], y)
         x = bias_act(y, b, nchw=last)
-    return x
+    return (x, x0) if bottom else x
 
   @torch.no_grad()
   def __call__(self, inputs):
+    return self.features(inputs)
+
+  @torch.no_grad()
+  def features(self, inputs, bottom=False):
+    """The left and right feature maps; bottom=True: (x, w, x0) with the left bottleneck x0 (what the value branch of the
+    dueling head pools, models.py:179-186) as [B, h, w, C] in this object's dtype, contiguous."""
     self._refresh()
     xm, xo = inputs
-    return self._unet(self.net.left, xm.contiguous()), self._unet(self.net.right, xo.contiguous())
+    if not bottom:
+      return self._unet(self.net.left, xm.contiguous()), self._unet(self.net.right, xo.contiguous())
+    x, x0 = self._unet(self.net.left, xm.contiguous(), bottom=True)
+    return x, self._unet(self.net.right, xo.contiguous()), x0.permute(0, 2, 3, 1).contiguous()
 
   @torch.no_grad()
   def pos(self, corr):
@@ -834,6 +896,8 @@ class FusedPolicy(object):
     self.fast = (autocast == torch.bfloat16) if fast is None else bool(fast)
     self._ff = None
 
+  ROUTING_BATCH = 8   # the largest batch multiple a layer's routing looks at (srl_conv3x3_gemm_batch_multiple)
+
   @staticmethod
   def draws(net, B, gen, device, mode='epsilon-greedy'):
     """The random numbers one call over B samples consumes, drawn as that call draws them (`draws=` of `__call__`: a
@@ -871,6 +935,97 @@ class FusedPolicy(object):
       adv = self._ff.pos(corr) if self.fast else net.pos(corr).flatten(1)
       out[s:e] = boltzmann_head(adv, keys[s:e], epsilon) if mode == 'boltzmann' else policy_head(adv, u[s:e], rnd[s:e], epsilon)
     return out
+
+
+  # ---------------------------------------------------------------------------------------------- greedy acting, evaluation
+  def _features(self, net, xm, xo):
+    """(left features, right features, left bottleneck [B, h, w, C]) of one chunk, by the path `__call__` takes."""
+    if self.fast:
+      if self._ff is None or self._ff.net is not net:
+        self._ff = FastFeatures(net, dtype=torch.bfloat16 if self.autocast == torch.bfloat16 else torch.float32)
+      return self._ff.features((xm, xo), bottom=True)
+    prep = net.prepare((xm, xo))
+    if self.autocast is not None:
+      with torch.autocast('cuda', dtype=self.autocast):
+        (x, x0), (w, _) = net.left(prep[0]), net.right(prep[1])
+    else:
+      (x, x0), (w, _) = net.left(prep[0]), net.right(prep[1])
+    return x, w, x0.permute(0, 2, 3, 1).contiguous()
+
+  @torch.no_grad()
+  def state_value(self, net, x0):
+    """The state value of the dueling head (`layers.value`, layers.py:424-436; models.py:179-186) from the left bottleneck
+    x0 [B, h, w, C]: float32 [B], or None for a net without the dueling head.  Average pooling: `srl_tvalue_fwd`, the kernel
+    of the update, on the float32 view of x0 with the weights of `net.value`; any other head: the module's own layers."""
+    if not getattr(net, 'dueling', False):
+      return None
+    B, h, w, C = x0.shape
+    x0 = x0.float().contiguous()
+    val = net.value
+    if net.dueling_avg_pool and len(val) == 3 and isinstance(val[0], torch.nn.Linear) and isinstance(val[2], torch.nn.Linear) and \
+       val[2].out_features == 1 and C <= 4096:
+      d1, d2 = val[0], val[2]
+      W1, b1, W2, b2 = (t.detach().float().contiguous() for t in (d1.weight, d1.bias, d2.weight, d2.bias))
+      v = torch.empty(B, dtype=torch.float32, device=x0.device)
+      with torch.cuda.device(x0.device):
+        rc = load().srl_tvalue_fwd(x0.data_ptr(), W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), None, None,
+                                   v.data_ptr(), B, h * w, C, int(d1.out_features), _stream(x0))
+      if rc:
+        raise RuntimeError(load().srl_train_conv_last_error().decode())
+      return v
+    pooled = x0.mean(dim=(1, 2)) if net.dueling_avg_pool else x0.amax(dim=(1, 2))
+    return val(pooled).reshape(B)
+
+  @torch.no_grad()
+  def greedy(self, net, inputs, n_valid=None, stats=False, values=False):
+    """Greedy acting on the rollout kernels (the head: include/stackrl_greedy.h): the forward of `__call__`, the state value,
+    then `greedy_head` — no [B, A] Q tensor unless `values` asks for it.  inputs[1] is [B, h, w, 1], or the Stack-v2 layout
+    of the vectorised env [B, G, h, w, 1] (G object maps per overhead map, the first `n_valid` valid): the left U-Net and the
+    value run once per env, the right U-Net on the B * G maps, and the action is r * A + p.  `chunk` counts
+    cross-correlation samples: an env chunk is chunk // G, rounded down to a multiple of ROUTING_BATCH (and at least that).
+    Returns actions [B] i64, then as asked stats [B, 4] f64 {max, min, sum, sum of squares of Q} and Q [B, G * A] f32."""
+    xm, xo = inputs
+    B = xm.shape[0]
+    grouped = xo.dim() == 5
+    G = xo.shape[1] if grouped else 1
+    if n_valid is not None and not 1 <= int(n_valid) <= G:
+      raise ValueError('n_valid must be in 1..{}, got {}'.format(G, n_valid))
+    # every chunk is evaluated as a multiple of ROUTING_BATCH envs (the last one padded with blank observations): which kernel
+    # a deep layer goes to depends on the batch (FastFeatures._gemm), and the cross-correlation is the row-product kernel at every
+    # batch size (`xcorr_forward_rows`); the hand-written kernels work sample by sample, so where no layer falls to the library
+    # (128 / 32, fp32-class) an env's result does not depend on the chunk size or on the batch it arrives in
+    R = self.ROUTING_BATCH
+    step = max(R, self.chunk // G // R * R)
+    actions = torch.empty(B, dtype=torch.int64, device=xm.device)
+    st = torch.empty((B, 4), dtype=torch.float64, device=xm.device) if stats else None
+    q = None
+    for s in range(0, B, step):
+      e = min(B, s + step)
+      cm, co = xm[s:e], xo[s:e]
+      n = e - s + (s - e) % R
+      if n > e - s:
+        cm = torch.cat((cm, cm.new_zeros((n - (e - s),) + tuple(cm.shape[1:]))))
+        co = torch.cat((co, co.new_zeros((n - (e - s),) + tuple(co.shape[1:]))))
+      x, w, x0 = self._features(net, cm, co.reshape(n * G, *co.shape[-3:]) if grouped else co)
+      v = self.state_value(net, x0)
+      if G > 1:                                    # the env's left feature map once per object map
+        x = x[:, None].expand(n, G, *x.shape[1:]).reshape(n * G, *x.shape[1:])
+      corr = xcorr_forward_rows(x, w)
+      adv = (self._ff.pos(corr) if self.fast else net.pos(corr).flatten(1)).reshape(n, G, -1)[:e - s]
+      v = v[:e - s] if v is not None else None
+      out = greedy_head(adv, v, n_valid, stats=stats, values=values)
+      out = out if isinstance(out, tuple) else (out,)
+      actions[s:e] = out[0]
+      if stats:
+        st[s:e] = out[1]
+      if values:
+        qc = out[-1].reshape(e - s, -1)
+        if q is None:
+          q = qc if e - s == B else torch.empty((B, qc.shape[1]), dtype=torch.float32, device=xm.device)
+        if q is not qc:
+          q[s:e] = qc
+    out = (actions,) + ((st,) if stats else ()) + ((q,) if values else ())
+    return out if len(out) > 1 else actions
 
 
 # ------------------------------------------------------------------------------------------------ update path (csrc/learner.hip)

@@ -24,7 +24,8 @@ class Trainer(object):
 
   def __init__(self, env, agent, eval_env=None, directory=None, log_interval=100, eval_interval=10000,
                checkpoint_interval=10000, eval_seed=None, train_reward_buffer_length=10, eval_reward_buffer_length=10,
-               save_evaluated_policies=False, log_to_file=True, checkpoint_memory=True, goal_check_interval=1000):
+               save_evaluated_policies=False, log_to_file=True, checkpoint_memory=True, goal_check_interval=1000,
+               fused_eval=False):
     """
     Args (training.py:40-103):
       env, agent: the vectorised environment and the DQN agent.
@@ -36,6 +37,8 @@ class Trainer(object):
       save_evaluated_policies: save the Q-net weights after every evaluation (:190-197, :386-387).
       checkpoint_memory: include the replay memory in checkpoints (the reference always does).
       goal_check_interval: with a curriculum, how often (iterations) the training return is checked against the goal.
+      fused_eval: `eval()` acts through `agent.greedy(stats=True)` and folds each step's per-env statistics of Q into running
+        float64 totals on the device instead of keeping every step's [B, A] values (the same eval.csv columns).
     """
     # curriculum (training.py:120-158): generators of (env, goal)
     self._curriculum = self._eval_curriculum = None
@@ -65,6 +68,7 @@ class Trainer(object):
     self._eval_seed = eval_seed
     self._save_weights = bool(save_evaluated_policies)
     self._checkpoint_memory = bool(checkpoint_memory)
+    self._fused_eval = bool(fused_eval)
     dev = agent.device
     self._reward = metrics.AverageReward(env.batch_size, length=train_reward_buffer_length, device=dev)
     self._eval_reward = metrics.AverageReward(eval_env.batch_size if eval_env is not None else 1,
@@ -265,6 +269,9 @@ class Trainer(object):
     step = env.reset()
     if callable(step):
       step = step()
+    if self._fused_eval:
+      row = (self.iterations,) + self._eval_streaming(env, agent, step)
+      return self._write_eval(row)
     values = []
     while not self._eval_reward.full:
       a, value = agent.policy(step[0], values=True)
@@ -276,6 +283,32 @@ class Trainer(object):
     values = torch.stack(values)                                   # [steps, B, A]
     row = (self.iterations, float(self._eval_reward.result), float(values.amax(dim=-1).mean()), float(values.mean()),
            float(values.std(unbiased=False)), float(values.min()), float(values.max()))
+    return self._write_eval(row)
+
+  def _eval_streaming(self, env, agent, step):
+    """The evaluation loop on `agent.greedy(stats=True)`: per step a [B, 4] float64 tensor {max, min, sum, sum of squares of
+    Q(s, .)} per env, folded on the device into the sum of the row maxima, the sum, the sum of squares, the minimum and the
+    maximum; one synchronisation at the end.  `values.std(unbiased=False)` becomes sqrt(S2 / N - (S1 / N)^2) in float64."""
+    tot = ext = None
+    rows = count = 0
+    while not self._eval_reward.full:
+      obs = step[0]
+      a, st = agent.greedy(obs, stats=True)
+      step = env.step(a)
+      if callable(step):
+        step = step()
+      self._eval_reward += step
+      s = st[:, [0, 2, 3]].sum(dim=0)
+      e = torch.stack((st[:, 1].min(), st[:, 0].max()))
+      tot = s if tot is None else tot + s
+      ext = e if ext is None else torch.stack((torch.minimum(ext[0], e[0]), torch.maximum(ext[1], e[1])))
+      rows += st.shape[0]
+      count += st.shape[0] * int(agent.q_net.n_actions) * (obs[1].shape[1] if obs[1].dim() == 5 else 1)
+    smax, s1, s2, lo, hi = torch.cat((tot, ext)).tolist()            # the one synchronisation
+    mean = s1 / count
+    return (float(self._eval_reward.result), smax / rows, mean, max(s2 / count - mean * mean, 0.0) ** 0.5, lo, hi)
+
+  def _write_eval(self, row):
     if self._eval_file is not None and self._rank == 0:
       header = '' if os.path.isfile(self._eval_file) else 'Iter,Return,Value,MeanValue,StdValue,MinValue,MaxValue\n'
       with open(self._eval_file, 'a') as f:
