@@ -36,8 +36,10 @@ class OrientationGreedy(object):
   """Batch-wise greedy policy for the vectorised Stack-v2 env: for every env the values of all its orientations,
   `model` evaluated on the expanded observation, and the action `orientation * A + pixel` of the overall maximum —
   what `Greedy(batchwise=True)` returns as `(index, action)` for one env (arg-max per row, then the best row; ties to
-  the lowest index, which is the lowest flat index).  `minimize=True` serves cost-like models (the heuristic
-  baselines, baselines.py:201-217)."""
+  the lowest index, which is the lowest flat index).  `minimize=True` takes the plain arg-min over all rows' values of a
+  cost-like model.  That is not the reference's heuristic baseline on Stack-v2, which applies the goal mask and the
+  local-minimum rule per row before it compares rows: for that policy call `stackrl_amd.baselines.Baseline` with the grouped
+  observation (include/stackrl_baseline_rows.h)."""
 
   def __init__(self, model, value=False, minimize=False):
     if not callable(model):
