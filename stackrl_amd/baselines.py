@@ -11,34 +11,13 @@ policy is the reference's `Baseline(batched=True, batchwise=True)` (`__main__.py
 the map whose returned value at its own action is the largest.  include/stackrl_baseline_rows.h states it; `Baseline`,
 `heuristic_values` and `select` take that layout as it is, `baseline_rows_reference` restates the choice on the CPU.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from stackrl_amd import qops
 
 METHODS = {'random': 0, 'correlate': 1, 'height': 2, 'difference': 3, 'corrcoef': 4}   # baselines.py:158-165
-
-
-def _lib():
-  L = qops.load()
-  if not getattr(L, '_heur_ready', False):
-    VP = ctypes.c_void_p
-    L.srl_heuristic.restype = ctypes.c_int
-    L.srl_heuristic.argtypes = [ctypes.c_int32, VP, VP, VP, VP] + [ctypes.c_int32] * 6 + [ctypes.c_double, VP]
-    L.srl_baseline_select.restype = ctypes.c_int
-    L.srl_baseline_select.argtypes = [VP, VP, ctypes.c_int32, ctypes.c_int32, VP, VP, ctypes.c_int32, ctypes.c_int32, VP]
-    L.srl_heuristic_rows.restype = ctypes.c_int
-    L.srl_heuristic_rows.argtypes = [ctypes.c_int32, VP, VP, VP, VP] + [ctypes.c_int32] * 8 + [ctypes.c_double, VP]
-    L.srl_baseline_rows_select.restype = ctypes.c_int
-    L.srl_baseline_rows_select.argtypes = [VP, VP] + [ctypes.c_int32] * 6 + [VP, VP, VP, VP]
-    L._heur_ready = True
-  return L
-
-
-def _stream(t):
-  return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+_lib = qops.load      # the library's one loader, under the name this module's callers used before `qops._SIGS` declared every export
 
 
 def _check_n_valid(n_valid, G):
@@ -82,7 +61,6 @@ def heuristic_values(method, inputs, mask=True, difference_exponent=2, weights_e
   h = xo.shape[2] if grouped else xo.shape[1]
   OH = H - h + 1
   mid = METHODS[method] if isinstance(method, str) else int(method)
-  L = _lib()
   if grouped:
     G = xo.shape[1]
     if xo.shape[0] != B:
@@ -93,19 +71,13 @@ def heuristic_values(method, inputs, mask=True, difference_exponent=2, weights_e
     else:
       vals = torch.empty((B, G, OH, OH), dtype=torch.float64, device=xm.device)
       mk = torch.empty((B, G, OH, OH), dtype=torch.uint8, device=xm.device) if mask else None
-    with torch.cuda.device(xm.device):
-      rc = L.srl_heuristic_rows(mid if mid else 2, xm.data_ptr(), xo.data_ptr(), vals.data_ptr(), mk.data_ptr() if mask else None,
-                                B, G, n_valid, H, h, int(difference_exponent), int(weights_exponent), int(bool(localized)),
-                                float(threshold), _stream(xm))
+    qops.call('srl_heuristic_rows', xm, mid if mid else 2, xm, xo, vals, mk, B, G, n_valid, H, h, int(difference_exponent),
+              int(weights_exponent), int(bool(localized)), float(threshold))
   else:
     vals = torch.empty((B, OH, OH), dtype=torch.float64, device=xm.device)
     mk = torch.empty((B, OH, OH), dtype=torch.uint8, device=xm.device) if mask else None
-    with torch.cuda.device(xm.device):
-      rc = L.srl_heuristic(mid if mid else 2, xm.data_ptr(), xo.data_ptr(), vals.data_ptr(), mk.data_ptr() if mask else None,
-                           B, H, h, int(difference_exponent), int(weights_exponent), int(bool(localized)), float(threshold),
-                           _stream(xm))
-  if rc:
-    raise RuntimeError(L.srl_qnet_last_error().decode())
+    qops.call('srl_heuristic', xm, mid if mid else 2, xm, xo, vals, mk, B, H, h, int(difference_exponent), int(weights_exponent),
+              int(bool(localized)), float(threshold))
   if mid == 0:   # 'random' keeps the mask of the heuristic pass and replaces the values (all B * G maps in one draw)
     vals = torch.rand(vals.shape, generator=generator, device=xm.device, dtype=torch.float64)
   return (vals, mk.bool()) if mask else vals
@@ -132,24 +104,14 @@ def select(values, mask=None, goal=True, minorder=1, value=False, n_valid=None, 
     raise ValueError('mask {} does not match the values {}'.format(tuple(mk.shape), tuple(values.shape)))
   actions = torch.empty(B, dtype=torch.int64, device=values.device)
   neg = torch.empty_like(values) if value else None
-  L = _lib()
   if grouped:
     G = values.shape[1]
     n_valid = _check_n_valid(n_valid, G)
     c = torch.empty((B, G), dtype=torch.float64, device=values.device) if chosen else None
-    with torch.cuda.device(values.device):
-      rc = L.srl_baseline_rows_select(values.data_ptr(), mk.data_ptr() if mk is not None else None, int(bool(goal)), int(minorder),
-                                      B, G, n_valid, OH, actions.data_ptr(), c.data_ptr() if chosen else None,
-                                      neg.data_ptr() if value else None, _stream(values))
-    if rc:
-      raise RuntimeError(L.srl_qnet_last_error().decode())
+    qops.call('srl_baseline_rows_select', values, values, mk, int(bool(goal)), int(minorder), B, G, n_valid, OH, actions, c, neg)
     out = (actions,) + ((c,) if chosen else ()) + ((neg,) if value else ())
     return out if len(out) > 1 else actions
-  with torch.cuda.device(values.device):
-    rc = L.srl_baseline_select(values.data_ptr(), mk.data_ptr() if mk is not None else None, int(bool(goal)), int(minorder),
-                               actions.data_ptr(), neg.data_ptr() if value else None, B, OH, _stream(values))
-  if rc:
-    raise RuntimeError(L.srl_qnet_last_error().decode())
+  qops.call('srl_baseline_select', values, values, mk, int(bool(goal)), int(minorder), actions, neg, B, OH)
   return (actions, neg) if value else actions
 
 

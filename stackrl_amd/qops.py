@@ -1,4 +1,6 @@
-"""Python side of libstackrl_qnet.so (include/stackrl_qnet.h, include/stackrl_explore.h, include/stackrl_greedy.h): the hand-written ops of the Q-net rollout path.
+"""Python side of libstackrl_qnet.so (include/stackrl_qnet.h, stackrl_explore.h, stackrl_greedy.h, stackrl_baseline_rows.h): the one
+signature table (`_SIGS`), loader (`load`) and checked launch (`call`) of the library, which qtrain.py and baselines.py use too,
+and the hand-written ops of the Q-net rollout path.
 No CPU fallback: these functions need a HIP device and the built library."""
 import ctypes
 import os
@@ -9,111 +11,121 @@ from stackrl_amd import build as _build
 
 _LIB = None
 
+_VP, _I32, _I64, _F32, _F64, _INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_int
+# every .hip file keeps the text of its last refusal in a buffer of its own: the accessor that goes with an export is the one
+# of the file that defines it (qnet.hip, greedy.hip and heuristics.hip share qnet.hip's)
+_QNET, _XCORR, _EPI, _CONV, _GEMM, _LEARN, _TRAIN = ('srl_qnet_last_error', 'srl_xcorr_mfma_last_error', 'srl_epilogue_last_error',
+                                                     'srl_conv_last_error', 'srl_conv_gemm_last_error', 'srl_learner_last_error',
+                                                     'srl_train_conv_last_error')
+# export -> (restype, argtypes, error accessor or None): every declaration of include/stackrl_qnet.h, stackrl_explore.h,
+# stackrl_greedy.h and stackrl_baseline_rows.h (pointers as void*); tests/test_abi.py holds the table to the headers and the
+# accessors to the sources.  A launching export returns int and takes the stream last; the others are plain queries.
+_SIGS = {
+  # csrc/qnet.hip, greedy.hip, heuristics.hip
+  'srl_xcorr_forward': (_INT, [_VP] * 3 + [_I32] * 6 + [_VP], _QNET),
+  'srl_policy_head': (_INT, [_VP] * 3 + [_F32, _VP, _I32, _I32, _VP], _QNET),
+  'srl_boltzmann_head': (_INT, [_VP, _VP, _F32, _VP, _I32, _I32, _VP], _QNET),
+  'srl_greedy_head': (_INT, [_VP] * 2 + [_I32] * 4 + [_VP] * 4, _QNET),
+  'srl_heuristic': (_INT, [_I32] + [_VP] * 4 + [_I32] * 6 + [_F64, _VP], _QNET),
+  'srl_baseline_select': (_INT, [_VP, _VP, _I32, _I32, _VP, _VP, _I32, _I32, _VP], _QNET),
+  'srl_heuristic_rows': (_INT, [_I32] + [_VP] * 4 + [_I32] * 8 + [_F64, _VP], _QNET),
+  'srl_baseline_rows_select': (_INT, [_VP] * 2 + [_I32] * 6 + [_VP] * 4, _QNET),
+  'srl_qnet_last_error': (ctypes.c_char_p, [], None),
+  'srl_qnet_build_info': (ctypes.c_char_p, [], None),
+  # csrc/xcorr_mfma.hip
+  'srl_xcorr_mfma_scratch_bytes': (_I64, [_I32] * 6, None),
+  'srl_xcorr_mfma': (_INT, [_I32, _I32, _VP, _I32, _VP, _I32, _VP, _VP, _I64] + [_I32] * 4 + [_VP], _XCORR),
+  'srl_xcorr_rows': (_INT, [_I32, _VP, _VP, _I32, _VP] + [_I32] * 4 + [_VP], _XCORR),
+  'srl_xcorr_mfma_last_error': (ctypes.c_char_p, [], None),
+  # csrc/epilogue.hip
+  'srl_bias_act': (_INT, [_VP] * 3 + [_I64] + [_I32] * 5 + [_VP], _EPI),
+  'srl_bias_act_f32': (_INT, [_VP] * 3 + [_I64] + [_I32] * 5 + [_VP], _EPI),
+  'srl_bias_act_pool': (_INT, [_VP] * 4 + [_I32] * 6 + [_VP], _EPI),
+  'srl_bias_act_pool_f32': (_INT, [_VP] * 4 + [_I32] * 6 + [_VP], _EPI),
+  'srl_bias_act_bwd_scratch_floats': (_I64, [_I64, _I32], None),
+  'srl_bias_act_bwd_f32': (_INT, [_VP] * 5 + [_I64, _I32, _I32, _VP], _EPI),
+  'srl_pool2x2': (_INT, [_VP] * 2 + [_I32] * 7 + [_VP], _EPI),
+  'srl_epilogue_last_error': (ctypes.c_char_p, [], None),
+  # csrc/conv_mfma.hip
+  'srl_conv3x3_wfrag_elems': (_I32, [_I32] * 2, None),
+  'srl_conv3x3_bias_relu': (_INT, [_VP] * 5 + [_I32] * 8 + [_VP], _CONV),
+  'srl_conv3x3_bias_relu_f32': (_INT, [_VP] * 5 + [_I32] * 8 + [_VP], _CONV),
+  'srl_conv3x3_thin': (_INT, [_VP, _I32, _VP, _VP, _VP] + [_I32] * 6 + [_VP], _CONV),
+  'srl_conv3x3_thin_f32': (_INT, [_VP, _I32, _VP, _VP, _VP] + [_I32] * 6 + [_VP], _CONV),
+  'srl_conv3x3_relu_project': (_INT, [_VP] * 4 + [_F32, _VP] + [_I32] * 5 + [_VP], _CONV),
+  'srl_conv3x3_relu_project_f32': (_INT, [_VP] * 4 + [_F32, _VP] + [_I32] * 5 + [_VP], _CONV),
+  'srl_thin_conv3x3_bias_relu_f32': (_INT, [_VP, _I32, _I32] + [_VP] * 6 + [_I32] * 6 + [_VP], _CONV),
+  'srl_thin_conv3x3_relu_project_f32': (_INT, [_VP] * 6 + [_F32, _VP] + [_I32] * 3 + [_VP], _CONV),
+  'srl_convt2x2_wfrag_elems': (_I32, [_I32] * 2, None),
+  'srl_convt2x2_bias_relu': (_INT, [_VP] * 4 + [_I32] * 7 + [_VP], _CONV),
+  'srl_convt2x2_bias_relu_f32': (_INT, [_VP] * 4 + [_I32] * 7 + [_VP], _CONV),
+  'srl_conv_last_error': (ctypes.c_char_p, [], None),
+  # csrc/conv_gemm.hip
+  'srl_conv3x3_gemm_supported': (_I32, [_I32] * 3, None),
+  'srl_conv3x3_gemm_wfrag_elems': (_I64, [_I32] * 2, None),
+  'srl_conv3x3_gemm_batch_multiple': (_I32, [_I32] * 2, None),
+  'srl_conv3x3_gemm_bias_relu': (_INT, [_VP] * 4 + [_I32] * 7 + [_VP], _GEMM),
+  'srl_convt2x2_gemm_supported': (_I32, [_I32] * 2, None),
+  'srl_convt2x2_gemm_bias_relu': (_INT, [_VP] * 4 + [_I32] * 8 + [_VP], _GEMM),
+  'srl_conv_gemm_last_error': (ctypes.c_char_p, [], None),
+  # csrc/learner.hip
+  'srl_td_epilogue': (_INT, [_VP] * 7 + [_F32, _F32, _F32, _I32, _F32, _I32, _I32] + [_VP] * 8, _LEARN),
+  'srl_adam_step': (_INT, [_VP] * 4 + [_I64, _VP] + [_F32] * 4 + [_VP], _LEARN),
+  'srl_gumbel_topk_scratch_bytes': (_I64, [_I64, _I32], None),
+  'srl_gumbel_topk': (_INT, [_VP] * 3 + [_I64, _I32] + [_VP] * 3 + [_I64, _VP], _LEARN),
+  'srl_replay_scatter': (_INT, [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _I32, _I64, _I64] + [_VP] * 7, _LEARN),
+  'srl_replay_gather': (_INT, [_VP, _I32, _I64, _I64, _I32, _VP, _VP, _VP, _I64, _I64] + [_VP] * 16, _LEARN),
+  'srl_logit_extrema_scratch_bytes': (_I64, [], None),
+  'srl_logit_extrema': (_INT, [_VP, _I64] + [_VP] * 4, _LEARN),
+  'srl_learner_last_error': (ctypes.c_char_p, [], None),
+  # csrc/train_conv.hip
+  'srl_tconv': (_INT, [_VP, _I32, _I32, _VP, _VP, _VP] + [_I32] * 10 + [_VP], _TRAIN),
+  'srl_twrw_scratch_floats': (_I64, [_I32] * 6, None),
+  'srl_twrw': (_INT, [_VP, _I32, _I32, _VP, _VP, _VP] + [_I32] * 7 + [_VP, _I32, _I32, _VP, _VP], _TRAIN),
+  'srl_tact_bwd_scratch_floats': (_I64, [_I64, _I32], None),
+  'srl_tact_bwd_blocks': (_I32, [_I64, _I32], None),
+  'srl_tact_bwd': (_INT, [_VP, _I32, _I32, _VP, _I32, _I32] + [_VP] * 4 + [_I32] * 6 + [_VP], _TRAIN),
+  'srl_trepack': (_INT, [_VP, _VP, _VP, _I32, _I64, _VP], _TRAIN),
+  'srl_thead_fwd': (_INT, [_VP] * 5 + [_I32, _I32, _VP], _TRAIN),
+  'srl_thead_bwd': (_INT, [_VP] * 8 + [_I32, _I32, _VP], _TRAIN),
+  'srl_tvalue_fwd': (_INT, [_VP] * 8 + [_I32] * 4 + [_VP], _TRAIN),
+  'srl_tvalue_bwd': (_INT, [_VP] * 12 + [_I32] * 4 + [_VP], _TRAIN),
+  'srl_tlayout': (_INT, [_VP, _I32, _I32, _VP] + [_I32] * 4 + [_VP], _TRAIN),
+  'srl_tcorr_grad': (_INT, [_VP, _I32, _VP, _VP, _I32, _I32, _I32, _VP], _TRAIN),
+  'srl_tflip': (_INT, [_VP, _VP, _I64, _I32, _VP], _TRAIN),
+  'srl_tu8_to_f32': (_INT, [_VP, _VP, _I64, _VP], _TRAIN),
+  'srl_train_conv_last_error': (ctypes.c_char_p, [], None),
+}
+
 
 def load():
+  """Load (building first if the library is missing) and return the ctypes library; a symbol of `_SIGS` it lacks fails here."""
   global _LIB
   if _LIB is None:
     if not os.path.isfile(_build.QLIB):
       _build.build()
-    L = ctypes.CDLL(_build.QLIB)
-    VP = ctypes.c_void_p
-    L.srl_xcorr_forward.restype = ctypes.c_int
-    L.srl_xcorr_forward.argtypes = [VP, VP, VP] + [ctypes.c_int32] * 6 + [VP]
-    L.srl_xcorr_mfma_scratch_bytes.restype = ctypes.c_int64
-    L.srl_xcorr_mfma_scratch_bytes.argtypes = [ctypes.c_int32] * 6
-    L.srl_xcorr_mfma.restype = ctypes.c_int
-    L.srl_xcorr_mfma.argtypes = [ctypes.c_int32, ctypes.c_int32, VP, ctypes.c_int32, VP, ctypes.c_int32, VP, VP,
-                                 ctypes.c_int64] + [ctypes.c_int32] * 4 + [VP]
-    L.srl_xcorr_mfma_last_error.restype = ctypes.c_char_p
-    L.srl_bias_act.restype = ctypes.c_int
-    L.srl_bias_act.argtypes = [VP, VP, VP, ctypes.c_int64] + [ctypes.c_int32] * 5 + [VP]
-    L.srl_bias_act_pool.restype = ctypes.c_int
-    L.srl_bias_act_pool.argtypes = [VP, VP, VP, VP] + [ctypes.c_int32] * 6 + [VP]
-    L.srl_bias_act_f32.restype = ctypes.c_int
-    L.srl_bias_act_f32.argtypes = [VP, VP, VP, ctypes.c_int64] + [ctypes.c_int32] * 5 + [VP]
-    L.srl_bias_act_pool_f32.restype = ctypes.c_int
-    L.srl_bias_act_pool_f32.argtypes = [VP, VP, VP, VP] + [ctypes.c_int32] * 6 + [VP]
-    L.srl_epilogue_last_error.restype = ctypes.c_char_p
-    L.srl_conv3x3_wfrag_elems.restype = ctypes.c_int32
-    L.srl_conv3x3_wfrag_elems.argtypes = [ctypes.c_int32] * 2
-    L.srl_conv3x3_bias_relu.restype = ctypes.c_int
-    L.srl_conv3x3_bias_relu.argtypes = [VP] * 5 + [ctypes.c_int32] * 8 + [VP]
-    L.srl_conv3x3_bias_relu_f32.restype = ctypes.c_int
-    L.srl_conv3x3_bias_relu_f32.argtypes = [VP] * 5 + [ctypes.c_int32] * 8 + [VP]
-    L.srl_conv_last_error.restype = ctypes.c_char_p
-    L.srl_convt2x2_wfrag_elems.restype = ctypes.c_int32
-    L.srl_convt2x2_wfrag_elems.argtypes = [ctypes.c_int32] * 2
-    L.srl_convt2x2_bias_relu.restype = ctypes.c_int
-    L.srl_convt2x2_bias_relu.argtypes = [VP] * 4 + [ctypes.c_int32] * 7 + [VP]
-    L.srl_conv3x3_thin.restype = ctypes.c_int
-    L.srl_conv3x3_thin.argtypes = [VP, ctypes.c_int32, VP, VP, VP] + [ctypes.c_int32] * 6 + [VP]
-    L.srl_bias_act_bwd_scratch_floats.restype = ctypes.c_int64
-    L.srl_bias_act_bwd_scratch_floats.argtypes = [ctypes.c_int64, ctypes.c_int32]
-    L.srl_bias_act_bwd_f32.restype = ctypes.c_int
-    L.srl_bias_act_bwd_f32.argtypes = [VP] * 5 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, VP]
-    L.srl_pool2x2.restype = ctypes.c_int
-    L.srl_pool2x2.argtypes = [VP, VP] + [ctypes.c_int32] * 7 + [VP]
-    L.srl_convt2x2_gemm_supported.restype = ctypes.c_int32
-    L.srl_convt2x2_gemm_supported.argtypes = [ctypes.c_int32] * 2
-    L.srl_convt2x2_gemm_bias_relu.restype = ctypes.c_int
-    L.srl_convt2x2_gemm_bias_relu.argtypes = [VP] * 4 + [ctypes.c_int32] * 8 + [VP]
-    L.srl_conv3x3_gemm_supported.restype = ctypes.c_int32
-    L.srl_conv3x3_gemm_supported.argtypes = [ctypes.c_int32] * 3
-    L.srl_conv3x3_gemm_batch_multiple.restype = ctypes.c_int32
-    L.srl_conv3x3_gemm_batch_multiple.argtypes = [ctypes.c_int32] * 2
-    L.srl_conv3x3_gemm_wfrag_elems.restype = ctypes.c_int64
-    L.srl_conv3x3_gemm_wfrag_elems.argtypes = [ctypes.c_int32] * 2
-    L.srl_conv3x3_gemm_bias_relu.restype = ctypes.c_int
-    L.srl_conv3x3_gemm_bias_relu.argtypes = [VP] * 4 + [ctypes.c_int32] * 7 + [VP]
-    L.srl_conv_gemm_last_error.restype = ctypes.c_char_p
-    L.srl_conv3x3_thin_f32.restype = ctypes.c_int
-    L.srl_conv3x3_thin_f32.argtypes = L.srl_conv3x3_thin.argtypes
-    L.srl_convt2x2_bias_relu_f32.restype = ctypes.c_int
-    L.srl_convt2x2_bias_relu_f32.argtypes = L.srl_convt2x2_bias_relu.argtypes
-    L.srl_conv3x3_relu_project_f32.restype = ctypes.c_int
-    L.srl_conv3x3_relu_project_f32.argtypes = [VP, VP, VP, VP, ctypes.c_float, VP] + [ctypes.c_int32] * 5 + [VP]
-    L.srl_thin_conv3x3_bias_relu_f32.restype = ctypes.c_int
-    L.srl_thin_conv3x3_bias_relu_f32.argtypes = [VP, ctypes.c_int32, ctypes.c_int32] + [VP] * 6 + [ctypes.c_int32] * 6 + [VP]
-    L.srl_thin_conv3x3_relu_project_f32.restype = ctypes.c_int
-    L.srl_thin_conv3x3_relu_project_f32.argtypes = [VP] * 6 + [ctypes.c_float, VP] + [ctypes.c_int32] * 3 + [VP]
-    L.srl_conv3x3_relu_project.restype = ctypes.c_int
-    L.srl_conv3x3_relu_project.argtypes = [VP, VP, VP, VP, ctypes.c_float, VP] + [ctypes.c_int32] * 5 + [VP]
-    L.srl_policy_head.restype = ctypes.c_int
-    L.srl_policy_head.argtypes = [VP, VP, VP, ctypes.c_float, VP, ctypes.c_int32, ctypes.c_int32, VP]
-    L.srl_boltzmann_head.restype = ctypes.c_int
-    L.srl_boltzmann_head.argtypes = [VP, VP, ctypes.c_float, VP, ctypes.c_int32, ctypes.c_int32, VP]
-    L.srl_xcorr_rows.restype = ctypes.c_int
-    L.srl_xcorr_rows.argtypes = [ctypes.c_int32, VP, VP, ctypes.c_int32, VP] + [ctypes.c_int32] * 4 + [VP]
-    L.srl_greedy_head.restype = ctypes.c_int
-    L.srl_greedy_head.argtypes = [VP, VP] + [ctypes.c_int32] * 4 + [VP, VP, VP, VP]
-    L.srl_tvalue_fwd.restype = ctypes.c_int
-    L.srl_tvalue_fwd.argtypes = [VP] * 8 + [ctypes.c_int32] * 4 + [VP]
-    L.srl_train_conv_last_error.restype = ctypes.c_char_p
-    L.srl_qnet_last_error.restype = ctypes.c_char_p
-    I32, I64, F = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    L.srl_td_epilogue.restype = ctypes.c_int
-    L.srl_td_epilogue.argtypes = [VP] * 7 + [F, F, F, I32, F, I32, I32] + [VP] * 7 + [VP]
-    L.srl_adam_step.restype = ctypes.c_int
-    L.srl_adam_step.argtypes = [VP, VP, VP, VP, I64, VP, F, F, F, F, VP]
-    L.srl_gumbel_topk_scratch_bytes.restype = I64
-    L.srl_gumbel_topk_scratch_bytes.argtypes = [I64, I32]
-    L.srl_gumbel_topk.restype = ctypes.c_int
-    L.srl_gumbel_topk.argtypes = [VP, VP, VP, I64, I32, VP, VP, VP, I64, VP]
-    L.srl_replay_scatter.restype = ctypes.c_int
-    L.srl_replay_scatter.argtypes = [VP, VP, I64, I64, VP, VP, VP, I32, I64, I64] + [VP] * 6 + [VP]
-    L.srl_replay_gather.restype = ctypes.c_int
-    L.srl_replay_gather.argtypes = [VP, I32, I64, I64, I32, VP, VP, VP, I64, I64] + [VP] * 15 + [VP]
-    L.srl_logit_extrema_scratch_bytes.restype = I64
-    L.srl_logit_extrema_scratch_bytes.argtypes = []
-    L.srl_logit_extrema.restype = ctypes.c_int
-    L.srl_logit_extrema.argtypes = [VP, I64, VP, VP, VP, VP]
-    L.srl_learner_last_error.restype = ctypes.c_char_p
-    _LIB = L
+    lib = ctypes.CDLL(_build.QLIB)
+    for name, (res, args, _) in _SIGS.items():
+      fn = getattr(lib, name)  # AttributeError = symbol missing: fail loudly
+      fn.restype = res
+      fn.argtypes = args
+    _LIB = lib
   return _LIB
 
 
 def _stream(t):
   return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def call(name, t, *args):
+  """One launch of the export `name` on the device and current stream of tensor `t`: tensors among `args` go as their
+  data pointers, None as NULL, the stream last; a non-zero return raises RuntimeError with the text of the export's own
+  error accessor (`_SIGS`)."""
+  lib = load()
+  with torch.cuda.device(t.device):
+    rc = getattr(lib, name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], _stream(t))
+  if rc:
+    raise RuntimeError(getattr(lib, _SIGS[name][2])().decode())
 
 
 _SCRATCH = {}
@@ -143,12 +155,8 @@ def _xcorr_mfma(mode, precision, a, k, B, C, H, kh):
   O = H - kh + 1
   shape = {0: (B, 1, O, O), 1: (B, C, H, H), 2: (B, C, kh, kh)}[mode]
   out = torch.empty(shape, dtype=torch.float32, device=a.device)
-  with torch.cuda.device(a.device):
-    rc = L.srl_xcorr_mfma(mode, precision, a.data_ptr(), int(a.dtype == torch.float32), k.data_ptr(),
-                          int(k.dtype == torch.float32), out.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                          B, C, H, kh, _stream(a))
-  if rc:
-    raise RuntimeError(L.srl_xcorr_mfma_last_error().decode())
+  call('srl_xcorr_mfma', a, mode, precision, a, int(a.dtype == torch.float32), k, int(k.dtype == torch.float32), out, scratch,
+       scratch.numel(), B, C, H, kh)
   return out
 
 
@@ -216,10 +224,7 @@ def xcorr_forward(x, w, precision=None):
   B, C, H, W = x.shape
   kh, kw = w.shape[-2:]
   out = torch.empty((B, 1, H - kh + 1, W - kw + 1), dtype=torch.float32, device=x.device)
-  with torch.cuda.device(x.device):
-    rc = load().srl_xcorr_forward(x.data_ptr(), w.data_ptr(), out.data_ptr(), B, C, H, W, kh, kw, _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_qnet_last_error().decode())
+  call('srl_xcorr_forward', x, x, w, out, B, C, H, W, kh, kw)
   return out
 
 
@@ -234,10 +239,7 @@ def xcorr_forward_rows(x, w):
   B, C = x.shape[:2]
   f32 = int(x.dtype == torch.float32)
   out = torch.empty((B, 1, 97, 97), dtype=torch.float32, device=x.device)
-  with torch.cuda.device(x.device):
-    rc = load().srl_xcorr_rows(BF16X3 if f32 else BF16, x.data_ptr(), w.data_ptr(), f32, out.data_ptr(), B, C, 128, 32, _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_xcorr_mfma_last_error().decode())
+  call('srl_xcorr_rows', x, BF16X3 if f32 else BF16, x, w, f32, out, B, C, 128, 32)
   return out
 
 
@@ -246,11 +248,7 @@ def policy_head(adv, u, rnd, epsilon):
   adv = adv.contiguous().float()
   B, A = adv.shape
   actions = torch.empty(B, dtype=torch.int64, device=adv.device)
-  with torch.cuda.device(adv.device):
-    rc = load().srl_policy_head(adv.data_ptr(), u.contiguous().data_ptr(), rnd.contiguous().data_ptr(),
-                                float(epsilon), actions.data_ptr(), B, A, _stream(adv))
-  if rc:
-    raise RuntimeError(load().srl_qnet_last_error().decode())
+  call('srl_policy_head', adv, adv, u.contiguous(), rnd.contiguous(), float(epsilon), actions, B, A)
   return actions
 
 
@@ -264,11 +262,7 @@ def boltzmann_head(adv, keys, temperature):
   if keys.dtype != torch.int64 or tuple(keys.shape) != (B, 2) or keys.device != adv.device:
     raise ValueError('keys must be an int64 [{}, 2] tensor on {}'.format(B, adv.device))
   actions = torch.empty(B, dtype=torch.int64, device=adv.device)
-  with torch.cuda.device(adv.device):
-    rc = load().srl_boltzmann_head(adv.data_ptr(), keys.contiguous().data_ptr(), float(temperature), actions.data_ptr(),
-                                   B, A, _stream(adv))
-  if rc:
-    raise RuntimeError(load().srl_qnet_last_error().decode())
+  call('srl_boltzmann_head', adv, adv, keys.contiguous(), float(temperature), actions, B, A)
   return actions
 
 
@@ -290,10 +284,7 @@ def greedy_head(adv, v=None, n_valid=None, stats=False, values=False):
   actions = torch.empty(B, dtype=torch.int64, device=adv.device)
   st = torch.empty((B, 4), dtype=torch.float64, device=adv.device) if stats else None
   q = torch.empty_like(adv) if values else None
-  with torch.cuda.device(adv.device):
-    rc = load().srl_greedy_head(adv.data_ptr(), _ptr(v), B, G, n_valid, A, actions.data_ptr(), _ptr(st), _ptr(q), _stream(adv))
-  if rc:
-    raise RuntimeError(load().srl_qnet_last_error().decode())
+  call('srl_greedy_head', adv, adv, v, B, G, n_valid, A, actions, st, q)
   out = (actions,) + ((st,) if stats else ()) + ((q,) if values else ())
   return out if len(out) > 1 else actions
 
@@ -317,11 +308,7 @@ def bias_act(y, bias, out=None, out_offset=0, relu=True, nchw=False):
   else:
     dst = y if out is None else out
     stride, hw = dst.shape[1], 0
-  fn = load().srl_bias_act_f32 if y.dtype == torch.float32 else load().srl_bias_act
-  with torch.cuda.device(y.device):
-    rc = fn(y.data_ptr(), dst.data_ptr(), bias.data_ptr(), B * H * W, C, stride, out_offset, hw, int(relu), _stream(y))
-  if rc:
-    raise RuntimeError(load().srl_epilogue_last_error().decode())
+  call('srl_bias_act_f32' if y.dtype == torch.float32 else 'srl_bias_act', y, y, dst, bias, B * H * W, C, stride, out_offset, hw, int(relu))
   return dst
 
 
@@ -344,13 +331,8 @@ class _BiasAct(torch.autograd.Function):
     gy = gy.contiguous(memory_format=_CL)
     gx = torch.empty_like(gy, memory_format=_CL)
     gb = torch.empty(C, dtype=torch.float32, device=y.device)
-    L = load()
-    scratch = torch.empty(L.srl_bias_act_bwd_scratch_floats(B * H * W, C), dtype=torch.float32, device=y.device)
-    with torch.cuda.device(y.device):
-      rc = L.srl_bias_act_bwd_f32(gy.data_ptr(), y.data_ptr(), gx.data_ptr(), gb.data_ptr(), scratch.data_ptr(), B * H * W, C,
-                                  int(ctx.relu), _stream(y))
-    if rc:
-      raise RuntimeError(L.srl_epilogue_last_error().decode())
+    scratch = torch.empty(load().srl_bias_act_bwd_scratch_floats(B * H * W, C), dtype=torch.float32, device=y.device)
+    call('srl_bias_act_bwd_f32', y, gy, y, gx, gb, scratch, B * H * W, C, int(ctx.relu))
     return gx, gb, None
 
 
@@ -374,11 +356,8 @@ def bias_act_pool(y, bias, skip, skip_offset):
   """relu(y + bias[c]) into the channel slice [skip_offset, skip_offset + C) of `skip`, plus its 2 x 2 max-pool."""
   B, C, H, W = y.shape
   pooled = torch.empty((B, C, H // 2, W // 2), dtype=y.dtype, device=y.device, memory_format=_CL)
-  fn = load().srl_bias_act_pool_f32 if y.dtype == torch.float32 else load().srl_bias_act_pool
-  with torch.cuda.device(y.device):
-    rc = fn(y.data_ptr(), skip.data_ptr(), pooled.data_ptr(), bias.data_ptr(), B, H, W, C, skip.shape[1], skip_offset, _stream(y))
-  if rc:
-    raise RuntimeError(load().srl_epilogue_last_error().decode())
+  call('srl_bias_act_pool_f32' if y.dtype == torch.float32 else 'srl_bias_act_pool', y, y, skip, pooled, bias, B, H, W, C, skip.shape[1],
+       skip_offset)
   return pooled
 
 
@@ -386,10 +365,7 @@ def pool2x2(buf, C, offset=0):
   """2 x 2 max-pool of the channel slice [offset, offset + C) of a channels-last bf16 / float32 buffer [B,Ctot,H,W]."""
   B, Ct, H, W = buf.shape
   pooled = torch.empty((B, C, H // 2, W // 2), dtype=buf.dtype, device=buf.device, memory_format=_CL)
-  with torch.cuda.device(buf.device):
-    rc = load().srl_pool2x2(buf.data_ptr(), pooled.data_ptr(), B, H, W, C, Ct, offset, int(buf.dtype == torch.float32), _stream(buf))
-  if rc:
-    raise RuntimeError(load().srl_epilogue_last_error().decode())
+  call('srl_pool2x2', buf, buf, pooled, B, H, W, C, Ct, offset, int(buf.dtype == torch.float32))
   return pooled
 
 
@@ -463,12 +439,8 @@ def conv3x3_bias_relu(x, wfrag, bias, cout, out=None, out_offset=0, pool=False, 
     stride = dst.shape[1]
   pooled = torch.empty((B, cout, H // 2, W // 2), dtype=x.dtype, device=x.device, memory_format=_CL) if pool else None
   # float32 tensors take the fp32-class kernel (bf16x3 products, wfrag from pack_conv3x3_weights_x3)
-  fn = load().srl_conv3x3_bias_relu_f32 if x.dtype == torch.float32 else load().srl_conv3x3_bias_relu
-  with torch.cuda.device(x.device):
-    rc = fn(x.data_ptr(), wfrag.data_ptr(), bias.data_ptr(), dst.data_ptr(), pooled.data_ptr() if pool else None, B, H, W, cin,
-            cout, stride, out_offset, int(nchw), _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_conv_last_error().decode())
+  call('srl_conv3x3_bias_relu_f32' if x.dtype == torch.float32 else 'srl_conv3x3_bias_relu', x, x, wfrag, bias, dst, pooled, B, H, W, cin,
+       cout, stride, out_offset, int(nchw))
   return (dst, pooled) if pool else dst
 
 
@@ -503,11 +475,7 @@ def conv3x3_gemm_bias_relu(x, wfrag, bias, cout, out=None, out_offset=0):
   B, cin, H, W = x.shape
   assert H == W
   dst = out if out is not None else torch.empty((B, cout, H, W), dtype=x.dtype, device=x.device, memory_format=_CL)
-  with torch.cuda.device(x.device):
-    rc = load().srl_conv3x3_gemm_bias_relu(x.data_ptr(), wfrag.data_ptr(), bias.data_ptr(), dst.data_ptr(), B, W, cin, cout,
-                                           dst.shape[1], out_offset, int(x.dtype == torch.float32), _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_conv_gemm_last_error().decode())
+  call('srl_conv3x3_gemm_bias_relu', x, x, wfrag, bias, dst, B, W, cin, cout, dst.shape[1], out_offset, int(x.dtype == torch.float32))
   return dst
 
 
@@ -542,11 +510,7 @@ def convt2x2_gemm_bias_relu(x, wfrag, bias, cout, out, out_offset=0):
   """relu(conv_transpose2d(x, k=2, s=2) + bias) of the deep levels (128 -> 64, 256 -> 128; any map size) into the channel
   slice of `out`, csrc/conv_gemm.hip k_convt2x2_gemm; bf16 or float32 (wfrag from pack_convt2x2_weights(w, x3=True))."""
   B, cin, H, W = x.shape
-  with torch.cuda.device(x.device):
-    rc = load().srl_convt2x2_gemm_bias_relu(x.data_ptr(), wfrag.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W, cin, cout,
-                                            out.shape[1], out_offset, int(x.dtype == torch.float32), _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_conv_gemm_last_error().decode())
+  call('srl_convt2x2_gemm_bias_relu', x, x, wfrag, bias, out, B, H, W, cin, cout, out.shape[1], out_offset, int(x.dtype == torch.float32))
   return out
 
 
@@ -555,12 +519,8 @@ def convt2x2_bias_relu(x, wfrag, bias, cout, out, out_offset=0):
   (channels-last, twice the spatial size of x), csrc/conv_mfma.hip.  bf16 tensors: bf16 MFMA; float32 tensors: the
   fp32-class kernel (wfrag from pack_convt2x2_weights_x3)."""
   B, cin, H, W = x.shape
-  fn = load().srl_convt2x2_bias_relu_f32 if x.dtype == torch.float32 else load().srl_convt2x2_bias_relu
-  with torch.cuda.device(x.device):
-    rc = fn(x.data_ptr(), wfrag.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W, cin, cout,
-                                       out.shape[1], out_offset, _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_conv_last_error().decode())
+  call('srl_convt2x2_bias_relu_f32' if x.dtype == torch.float32 else 'srl_convt2x2_bias_relu', x, x, wfrag, bias, out, B, H, W, cin, cout,
+       out.shape[1], out_offset)
   return out
 
 
@@ -576,12 +536,8 @@ def conv3x3_thin(x, w, bias, out=None, dtype=torch.bfloat16):
   B, H, W, cin = x.shape
   if out is None:
     out = torch.empty((B, 16, H, W), dtype=dtype, device=x.device, memory_format=_CL)
-  fn = load().srl_conv3x3_thin_f32 if out.dtype == torch.float32 else load().srl_conv3x3_thin
-  with torch.cuda.device(x.device):
-    rc = fn(x.data_ptr(), int(x.dtype != torch.uint8), w.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                 B, H, W, cin, out.shape[2], out.shape[3], _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_conv_last_error().decode())
+  call('srl_conv3x3_thin_f32' if out.dtype == torch.float32 else 'srl_conv3x3_thin', x, x, int(x.dtype != torch.uint8), w, bias, out,
+       B, H, W, cin, out.shape[2], out.shape[3])
   return out
 
 
@@ -589,12 +545,8 @@ def conv3x3_relu_project(x, wfrag, bias, proj_w, proj_b, hv, wv):
   """sum_c proj_w[c] relu(conv3x3(x)[c] + bias[c]) + proj_b, float32 [B,hv,wv]: the last two layers of `pos_layers`."""
   B, _, H, W = x.shape
   out = torch.empty((B, hv, wv), dtype=torch.float32, device=x.device)
-  fn = load().srl_conv3x3_relu_project_f32 if x.dtype == torch.float32 else load().srl_conv3x3_relu_project
-  with torch.cuda.device(x.device):
-    rc = fn(x.data_ptr(), wfrag.data_ptr(), bias.data_ptr(), proj_w.data_ptr(), float(proj_b),
-                                         out.data_ptr(), B, H, W, hv, wv, _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_conv_last_error().decode())
+  call('srl_conv3x3_relu_project_f32' if x.dtype == torch.float32 else 'srl_conv3x3_relu_project', x, x, wfrag, bias, proj_w, float(proj_b),
+       out, B, H, W, hv, wv)
   return out
 
 
@@ -611,12 +563,8 @@ def thin_conv3x3_bias_relu(x, w1, b1, wfrag, bias, out=None, out_offset=0, pool=
     dst = out if out is not None else torch.empty((B, 16, H, W), dtype=torch.float32, device=x.device, memory_format=_CL)
     stride = dst.shape[1]
   pooled = torch.empty((B, 16, H // 2, W // 2), dtype=torch.float32, device=x.device, memory_format=_CL) if pool else None
-  with torch.cuda.device(x.device):
-    rc = load().srl_thin_conv3x3_bias_relu_f32(x.data_ptr(), int(x.dtype != torch.uint8), cin, w1.data_ptr(), b1.data_ptr(),
-                                               wfrag.data_ptr(), bias.data_ptr(), dst.data_ptr(), pooled.data_ptr() if pool else None,
-                                               B, H, W, stride, out_offset, int(nchw), _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_conv_last_error().decode())
+  call('srl_thin_conv3x3_bias_relu_f32', x, x, int(x.dtype != torch.uint8), cin, w1, b1, wfrag, bias, dst, pooled, B, H, W, stride,
+       out_offset, int(nchw))
   return (dst, pooled) if pool else dst
 
 
@@ -625,11 +573,7 @@ def thin_conv3x3_relu_project(x, w1, b1, wfrag, bias, proj_w, proj_b):
   `conv3x3_thin` into a zero-margined map followed by `conv3x3_relu_project`."""
   B, H, W = x.shape
   out = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
-  with torch.cuda.device(x.device):
-    rc = load().srl_thin_conv3x3_relu_project_f32(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), wfrag.data_ptr(), bias.data_ptr(),
-                                                  proj_w.data_ptr(), float(proj_b), out.data_ptr(), B, H, W, _stream(x))
-  if rc:
-    raise RuntimeError(load().srl_conv_last_error().decode())
+  call('srl_thin_conv3x3_relu_project_f32', x, x, w1, b1, wfrag, bias, proj_w, float(proj_b), out, B, H, W)
   return out
 
 
@@ -714,40 +658,55 @@ class FastFeatures(object):
     self._wt = {}
     self._wg = _LazyPacked()
     self._w1 = _LazyPacked()        # transposed convolutions left to the float32 1 x 1 form of the update's kernel (srl_tconv)
+    packers = {'conv_mfma': (self._wf, pack_conv3x3_weights), 'gemm': (self._wg, pack_conv3x3_gemm_weights),
+               'convt_mfma': (self._wf, pack_convt2x2_weights), 'convt_gemm': (self._wg, pack_convt2x2_weights)}
     for m in self.net.modules():
-      if isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d)):
-        self._w[m] = _WeightBias(m, self.dtype)
-        if self.mfma_conv and isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and \
-           m.in_channels in (16, 32, 64) and m.out_channels in (16, 32):
-          self._wf.offer(m, lambda m=m: pack_conv3x3_weights(m.weight))
-        if self.x3_conv and isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and \
-           m.in_channels in (16, 32, 64) and m.out_channels in (16, 32):
-          self._wf.offer(m, lambda m=m: pack_conv3x3_weights_x3(m.weight))
-        # the deep levels (64 / 128 / 256 output channels): implicit GEMM on the matrix cores (csrc/conv_gemm.hip)
-        if (self.mfma_conv or self.x3_conv) and isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and \
-           m.out_channels in (64, 128, 256) and m.in_channels % 32 == 0:
-          self._wg.offer(m, lambda m=m: pack_conv3x3_gemm_weights(m.weight, x3=self.x3_conv))
-        if (self.mfma_conv or self.x3_conv) and isinstance(m, torch.nn.ConvTranspose2d) and m.kernel_size == (2, 2) and \
-           (m.in_channels, m.out_channels) in ((32, 16), (64, 32)):
-          self._wf.offer(m, lambda m=m: pack_convt2x2_weights(m.weight, x3=not self.mfma_conv))
-        if (self.mfma_conv or self.x3_conv) and isinstance(m, torch.nn.ConvTranspose2d) and m.kernel_size == (2, 2) and \
-           (m.in_channels, m.out_channels) in ((128, 64), (256, 128)):
-          self._wg.offer(m, lambda m=m: pack_convt2x2_weights(m.weight, x3=not self.mfma_conv))
-        # float32 rollout: any other 2 x 2 stride-2 transposed convolution (the right U-Net's 64 -> 32 at 8 x 8, whose rows
-        # are narrower than the MFMA kernel's 16-pixel tiles) as a 1 x 1 convolution to 4 cout channels + depth-to-space in
-        # true float32 on the matrix cores (csrc/train_conv.hip k_tconv): weights [cin][q cout + co], q = 2 dy + dx
-        if self.x3_conv and isinstance(m, torch.nn.ConvTranspose2d) and m.kernel_size == (2, 2) and m.stride == (2, 2) and \
-           m.out_channels % 4 == 0 and (4 * m.out_channels) % 16 == 0:
-          self._w1.offer(m, lambda m=m: m.weight.detach().float().permute(0, 2, 3, 1).reshape(m.in_channels, 4 * m.out_channels).contiguous())
-        if (self.mfma_conv or self.x3_conv) and isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and \
-           m.in_channels in (1, 2) and m.out_channels == 16:
-          self._wt[m] = pack_thin_weights(m.weight)
+      if not isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d)):
+        continue
+      self._w[m] = _WeightBias(m, self.dtype)
+      family = self._family(m)
+      if family == 'thin':
+        self._wt[m] = pack_thin_weights(m.weight)
+      elif family in packers:
+        store, pack = packers[family]
+        store.offer(m, lambda m=m, pack=pack: pack(m.weight, x3=self.x3_conv))
+      # weights [cin][q cout + co], q = 2 dy + dx.  A convt_mfma layer keeps this form beside its own: that kernel wants rows of
+      # whole 16-pixel tiles (the right U-Net's 64 -> 32 at 8 x 8 has none); convt_gemm takes any map size and needs no second form
+      if family == 'tconv' or (family == 'convt_mfma' and self._tconv_ok(m)):
+        self._w1.offer(m, lambda m=m: m.weight.detach().float().permute(0, 2, 3, 1).reshape(m.in_channels, 4 * m.out_channels).contiguous())
     pos = getattr(self.net, 'pos', None)
     self._pos = None
     if (self.mfma_conv or self.x3_conv) and pos is not None and len(pos) == 5 and pos[0] in self._wt and pos[2] in self._wf and \
        pos[4].kernel_size == (1, 1) and pos[4].in_channels == 16 and pos[4].out_channels == 1:
       self._pos = (pos[4].weight.detach().float().reshape(16).contiguous(), float(pos[4].bias.detach()))
     self._key = key
+
+  def _tconv_ok(self, m):
+    return self.x3_conv and m.stride == (2, 2) and m.out_channels % 4 == 0      # 4 cout: a multiple of srl_tconv's 16
+
+  def _family(self, m):
+    """The hand-written kernel family of a convolution module, by its type and channel counts (None: the library convolution +
+    the fused epilogues).  Whether the family's kernel takes the layer at a given map size and batch is the routers' business."""
+    if not (self.mfma_conv or self.x3_conv):
+      return None
+    cin, cout = m.in_channels, m.out_channels
+    if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3):
+      if cin in (1, 2) and cout == 16:
+        return 'thin'                # the first layers, on the vector ALU
+      if cin in (16, 32, 64) and cout in (16, 32):
+        return 'conv_mfma'           # csrc/conv_mfma.hip: bf16, or bf16x3 products in the fp32-class mode
+      if cout in (64, 128, 256) and cin % 32 == 0:
+        return 'gemm'                # the deep levels: implicit GEMM on the matrix cores (csrc/conv_gemm.hip)
+    if isinstance(m, torch.nn.ConvTranspose2d) and m.kernel_size == (2, 2):
+      if (cin, cout) in ((32, 16), (64, 32)):
+        return 'convt_mfma'
+      if (cin, cout) in ((128, 64), (256, 128)):
+        return 'convt_gemm'
+      # float32 rollout: any other 2 x 2 stride-2 transposed convolution as a 1 x 1 convolution to 4 cout channels +
+      # depth-to-space in true float32 on the matrix cores (csrc/train_conv.hip k_tconv, the update's kernel)
+      if self._tconv_ok(m):
+        return 'tconv'
+    return None
 
   def _mine(self, m, x):
     return m in self._wf and x.shape[2] % 16 == 0 and x.shape[3] % 16 == 0
@@ -760,10 +719,43 @@ class FastFeatures(object):
     w, b = self._w[m]
     return _cl(torch.nn.functional.conv2d(x, w, None, padding=m.padding)), b
 
+  def _conv3x3(self, m, x, form='plain', cat=None, mfma=True, gemm=True):
+    """relu(conv3x3(x) + bias) of module m by the first of conv_mfma, the implicit GEMM and the library convolution + epilogue
+    that takes the layer at this map size and batch; mfma / gemm = False: that family is not tried at this position.
+    form 'plain': returns the output, channels-last; 'nchw': NCHW-contiguous (the GEMM has no such store: gemm=False goes with it);
+    'slice+pool': the output goes to the second half of the decoder's concat buffer `cat`, its 2 x 2 max-pool is returned."""
+    f, b = m.out_channels, self._w[m][1]
+    if mfma and self._mine(m, x):
+      if form == 'slice+pool':
+        return conv3x3_bias_relu(x, self._wf[m], b, f, out=cat, out_offset=f, pool=True)[1]
+      return conv3x3_bias_relu(x, self._wf[m], b, f, nchw=form == 'nchw')
+    if gemm and self._gemm(m, x):
+      if form == 'slice+pool':
+        conv3x3_gemm_bias_relu(x, self._wg[m], b, f, out=cat, out_offset=f)
+        return pool2x2(cat, f, f)
+      return conv3x3_gemm_bias_relu(x, self._wg[m], b, f)
+    y, b = self._conv(m, x)
+    return bias_act_pool(y, b, cat, f) if form == 'slice+pool' else bias_act(y, b, nchw=form == 'nchw')
+
+  def _upconv(self, up, x, cat):
+    """relu(conv_transpose2d(x, k=2, s=2) + bias) of module `up` into the first half of the concat buffer `cat`
+    (Concatenate([up, skip]) without a copy)."""
+    f, b = up.out_channels, self._w[up][1]
+    cl = x.is_contiguous(memory_format=_CL)
+    if up in self._wf and x.shape[3] % 16 == 0 and cl:
+      convt2x2_bias_relu(x, self._wf[up], b, f, cat, 0)
+    elif up in self._wg and cl:
+      convt2x2_gemm_bias_relu(x, self._wg[up], b, f, cat, 0)
+    elif up in self._w1 and x.dtype == torch.float32 and cl and cat.is_contiguous(memory_format=_CL):
+      from stackrl_amd import qtrain                    # channels-last tensors are [B, H, W, C] in memory
+      qtrain.tconv(qtrain.Act(x.permute(0, 2, 3, 1)), self._w1[up], b, 4 * f, taps=1, relu=True, out=(cat.permute(0, 2, 3, 1), 0), d2s=f)
+    else:
+      y = _cl(torch.nn.functional.conv_transpose2d(x, self._w[up][0], None, stride=up.stride))
+      bias_act(y, b, out=cat, out_offset=0)
+
   def _unet(self, U, obs, bottom=False):
     """obs: the env's uint8 observation [B,H,W,c] (channels-last memory).  bottom: also return the bottleneck (the output of
     the bottom block), channels-last."""
-    F = torch.nn.functional
     B = obs.shape[0]
     cats = []
     x = None
@@ -781,63 +773,22 @@ class FastFeatures(object):
       elif x is None:
         # uint8 NHWC / 255 (models.py:144-147); the NHWC memory is exactly a channels-last NCHW tensor
         x = (obs.float() / 255.0).to(self.dtype).permute(0, 3, 1, 2)
-        y, b = self._conv(blk[0], x)
-        bias_act(y, b)
-      elif self._mine(blk[0], x):
-        y = conv3x3_bias_relu(x, self._wf[blk[0]], self._w[blk[0]][1], f)
-      elif self._gemm(blk[0], x):
-        y = conv3x3_gemm_bias_relu(x, self._wg[blk[0]], self._w[blk[0]][1], f)
+        y = self._conv3x3(blk[0], x, mfma=False, gemm=False)      # a first layer that is not thin stays with the library
       else:
-        y, b = self._conv(blk[0], x)
-        bias_act(y, b)
+        y = self._conv3x3(blk[0], x)
       cat = torch.empty((B, 2 * f, y.shape[2], y.shape[3]), dtype=y.dtype, device=y.device, memory_format=_CL)
-      if self._mine(blk[2], y):                     # skip -> second half of the decoder's concat buffer, + pooled
-        _, x = conv3x3_bias_relu(y, self._wf[blk[2]], self._w[blk[2]][1], f, out=cat, out_offset=f, pool=True)
-      elif self._gemm(blk[2], y):
-        conv3x3_gemm_bias_relu(y, self._wg[blk[2]], self._w[blk[2]][1], f, out=cat, out_offset=f)
-        x = pool2x2(cat, f, f)
-      else:
-        y, b = self._conv(blk[2], y)
-        x = bias_act_pool(y, b, cat, f)
+      x = self._conv3x3(blk[2], y, 'slice+pool', cat)
       cats.append(cat)
     for m in (U.bottom[0], U.bottom[2]):
-      if self._gemm(m, x):
-        x = conv3x3_gemm_bias_relu(x, self._wg[m], self._w[m][1], m.out_channels)
-      else:
-        y, b = self._conv(m, x)
-        x = bias_act(y, b)
+      x = self._conv3x3(m, x, mfma=False)                         # the bottom block tries only the GEMM
     x0 = x
     n = len(U.up)
     for k, (up, blk) in enumerate(zip(U.up, U.upconv)):
       cat = cats.pop()
-      f = up.out_channels
-      b = self._w[up][1]
-      if up in self._wf and x.shape[3] % 16 == 0 and x.is_contiguous(memory_format=_CL):
-        convt2x2_bias_relu(x, self._wf[up], b, f, cat, 0)
-      elif up in self._wg and x.is_contiguous(memory_format=_CL):
-        convt2x2_gemm_bias_relu(x, self._wg[up], b, f, cat, 0)
-      elif up in self._w1 and x.dtype == torch.float32 and x.is_contiguous(memory_format=_CL) and cat.is_contiguous(memory_format=_CL):
-        from stackrl_amd import qtrain                    # channels-last tensors are [B, H, W, C] in memory
-        qtrain.tconv(qtrain.Act(x.permute(0, 2, 3, 1)), self._w1[up], b, 4 * f, taps=1, relu=True,
-                     out=(cat.permute(0, 2, 3, 1), 0), d2s=f)
-      else:
-        y = _cl(F.conv_transpose2d(x, self._w[up][0], None, stride=up.stride))
-        bias_act(y, b, out=cat, out_offset=0)       # Concatenate([up, skip]) without a copy
-      if self._mine(blk[0], cat):
-        y = conv3x3_bias_relu(cat, self._wf[blk[0]], self._w[blk[0]][1], f)
-      elif self._gemm(blk[0], cat):
-        y = conv3x3_gemm_bias_relu(cat, self._wg[blk[0]], self._w[blk[0]][1], f)
-      else:
-        y, b = self._conv(blk[0], cat)
-        bias_act(y, b)
-      last = k == n - 1
-      if self._mine(blk[2], y):
-        x = conv3x3_bias_relu(y, self._wf[blk[2]], self._w[blk[2]][1], f, nchw=last)
-      elif self._gemm(blk[2], y) and not last:
-        x = conv3x3_gemm_bias_relu(y, self._wg[blk[2]], self._w[blk[2]][1], f)
-      else:
-        y, b = self._conv(blk[2], y)
-        x = bias_act(y, b, nchw=last)
+      self._upconv(up, x, cat)
+      y = self._conv3x3(blk[0], cat)
+      last = k == n - 1                                           # the features leave NCHW-contiguous: never the GEMM
+      x = self._conv3x3(blk[2], y, 'nchw' if last else 'plain', gemm=not last)
     return (x, x0) if bottom else x
 
   @torch.no_grad()
@@ -896,6 +847,12 @@ class FusedPolicy(object):
     self.fast = (autocast == torch.bfloat16) if fast is None else bool(fast)
     self._ff = None
 
+  def _fast(self, net):
+    """The `FastFeatures` of `net` (one object, rebuilt when another net arrives)."""
+    if self._ff is None or self._ff.net is not net:
+      self._ff = FastFeatures(net, dtype=torch.bfloat16 if self.autocast == torch.bfloat16 else torch.float32)
+    return self._ff
+
   ROUTING_BATCH = 8   # the largest batch multiple a layer's routing looks at (srl_conv3x3_gemm_batch_multiple)
 
   @staticmethod
@@ -923,9 +880,7 @@ class FusedPolicy(object):
     for s in range(0, B, self.chunk):
       e = min(B, s + self.chunk)
       if self.fast:
-        if self._ff is None or self._ff.net is not net:
-          self._ff = FastFeatures(net, dtype=torch.bfloat16 if self.autocast == torch.bfloat16 else torch.float32)
-        x, w = self._ff((xm[s:e], xo[s:e]))
+        x, w = self._fast(net)((xm[s:e], xo[s:e]))
       elif self.autocast is not None:
         with torch.autocast('cuda', dtype=self.autocast):
           x, _, w = net.features((xm[s:e], xo[s:e]))
@@ -941,9 +896,7 @@ class FusedPolicy(object):
   def _features(self, net, xm, xo):
     """(left features, right features, left bottleneck [B, h, w, C]) of one chunk, by the path `__call__` takes."""
     if self.fast:
-      if self._ff is None or self._ff.net is not net:
-        self._ff = FastFeatures(net, dtype=torch.bfloat16 if self.autocast == torch.bfloat16 else torch.float32)
-      return self._ff.features((xm, xo), bottom=True)
+      return self._fast(net).features((xm, xo), bottom=True)
     prep = net.prepare((xm, xo))
     if self.autocast is not None:
       with torch.autocast('cuda', dtype=self.autocast):
@@ -967,11 +920,7 @@ class FusedPolicy(object):
       d1, d2 = val[0], val[2]
       W1, b1, W2, b2 = (t.detach().float().contiguous() for t in (d1.weight, d1.bias, d2.weight, d2.bias))
       v = torch.empty(B, dtype=torch.float32, device=x0.device)
-      with torch.cuda.device(x0.device):
-        rc = load().srl_tvalue_fwd(x0.data_ptr(), W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), None, None,
-                                   v.data_ptr(), B, h * w, C, int(d1.out_features), _stream(x0))
-      if rc:
-        raise RuntimeError(load().srl_train_conv_last_error().decode())
+      call('srl_tvalue_fwd', x0, x0, W1, b1, W2, b2, None, None, v, B, h * w, C, int(d1.out_features))
       return v
     pooled = x0.mean(dim=(1, 2)) if net.dueling_avg_pool else x0.amax(dim=(1, 2))
     return val(pooled).reshape(B)
@@ -1029,15 +978,6 @@ class FusedPolicy(object):
 
 
 # ------------------------------------------------------------------------------------------------ update path (csrc/learner.hip)
-def _lchk(rc):
-  if rc:
-    raise RuntimeError(load().srl_learner_last_error().decode())
-
-
-def _ptr(t):
-  return None if t is None else t.data_ptr()
-
-
 def td_epilogue(q, q_next_online, q_next_target, actions, rewards, terminal, weights, gamma, huber_delta, reward_scale,
                 double, prio_eps, ws):
   """Loss, mean TD, |TD|, new priorities and d loss / d Q(s, .) of `DQN.train` (dqn.py:408-476) in one launch.
@@ -1055,20 +995,14 @@ def td_epilogue(q, q_next_online, q_next_target, actions, rewards, terminal, wei
   term = terminal.contiguous().view(torch.uint8)
   act = actions.contiguous(); rew = rewards.contiguous().float()
   wts = weights.contiguous().float() if weights is not None else None
-  with torch.cuda.device(dev):
-    _lchk(load().srl_td_epilogue(q.data_ptr(), _ptr(qo), qt.data_ptr(), act.data_ptr(), rew.data_ptr(), term.data_ptr(),
-                                 _ptr(wts), float(gamma),
-                                 -1.0 if huber_delta is None else float(huber_delta), float(reward_scale or 0.0), int(bool(double)),
-                                 float(prio_eps), mb, A, out.data_ptr(), out[1:].data_ptr(), td_abs.data_ptr(), logits.data_ptr(),
-                                 grad_q.data_ptr(), ws['scratch'].data_ptr(), ws['ticket'].data_ptr(), _stream(q)))
+  call('srl_td_epilogue', q, q, qo, qt, act, rew, term, wts, float(gamma), -1.0 if huber_delta is None else float(huber_delta),
+       float(reward_scale or 0.0), int(bool(double)), float(prio_eps), mb, A, out, out[1:], td_abs, logits, grad_q, ws['scratch'], ws['ticket'])
   return out[0], out[1], td_abs, logits, grad_q
 
 
 def adam_step(params, grads, m, v, state, lr, beta1, beta2, eps):
   """Keras Adam over flat fp32 buckets, in place; `state` = 4 device floats {t, beta1^t, beta2^t, lr_t}."""
-  with torch.cuda.device(params.device):
-    _lchk(load().srl_adam_step(params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(), params.numel(), state.data_ptr(),
-                               float(lr), float(beta1), float(beta2), float(eps), _stream(params)))
+  call('srl_adam_step', params, params, grads, m, v, params.numel(), state, float(lr), float(beta1), float(beta2), float(eps))
 
 
 def gumbel_topk(logits, u, alpha_t, k, ws):
@@ -1080,9 +1014,7 @@ def gumbel_topk(logits, u, alpha_t, k, ws):
     ws['topk_scratch'] = torch.empty(need, dtype=torch.uint8, device=logits.device)
   idx = torch.empty(k, dtype=torch.int64, device=logits.device)
   key = torch.empty(k, dtype=torch.float32, device=logits.device)
-  with torch.cuda.device(logits.device):
-    _lchk(load().srl_gumbel_topk(logits.data_ptr(), u.data_ptr(), alpha_t.data_ptr(), n, k, idx.data_ptr(), key.data_ptr(),
-                                 ws['topk_scratch'].data_ptr(), need, _stream(logits)))
+  call('srl_gumbel_topk', logits, logits, u, alpha_t, n, k, idx, key, ws['topk_scratch'], need)
   return idx, key
 
 
@@ -1092,10 +1024,8 @@ def replay_scatter(state, reward, terminal, action, slot, part_len, mem_states, 
   B = s0.shape[0]
   b0, b1 = s0[0].numel() * s0.element_size(), s1[0].numel() * s1.element_size()
   r = reward.contiguous().float(); t = terminal.contiguous().to(torch.bool).view(torch.uint8); a = action.contiguous().to(torch.int64)
-  with torch.cuda.device(s0.device):
-    _lchk(load().srl_replay_scatter(s0.data_ptr(), s1.data_ptr(), b0, b1, r.data_ptr(), t.data_ptr(), a.data_ptr(), B, int(slot),
-                                    int(part_len), mem_states[0].data_ptr(), mem_states[1].data_ptr(), mem_reward.data_ptr(),
-                                    mem_terminal.data_ptr(), mem_action.data_ptr(), mem_logits.data_ptr(), _stream(s0)))
+  call('srl_replay_scatter', s0, s0, s1, b0, b1, r, t, a, B, int(slot), int(part_len), mem_states[0], mem_states[1], mem_reward,
+       mem_terminal, mem_action, mem_logits)
 
 
 def logit_extrema(logits, ws):
@@ -1106,8 +1036,7 @@ def logit_extrema(logits, ws):
     ws['ext'] = torch.empty(int(load().srl_logit_extrema_scratch_bytes()), dtype=torch.uint8, device=dev)
   v = torch.empty(2, dtype=torch.float32, device=dev)
   i = torch.empty(2, dtype=torch.int64, device=dev)
-  with torch.cuda.device(dev):
-    _lchk(load().srl_logit_extrema(logits.data_ptr(), logits.numel(), v.data_ptr(), i.data_ptr(), ws['ext'].data_ptr(), _stream(logits)))
+  call('srl_logit_extrema', logits, logits, logits.numel(), v, i, ws['ext'])
   return (v[0], i[0]), (v[1], i[1])
 
 
@@ -1124,10 +1053,6 @@ def replay_gather(idx, part_len, n_steps, literal_next, mem_states, mem_reward, 
   rew = torch.empty(mb, dtype=torch.float32, device=dev)
   term = torch.empty(mb, dtype=torch.bool, device=dev)
   w = torch.empty(mb, dtype=torch.float32, device=dev) if alpha_t is not None else None
-  with torch.cuda.device(dev):
-    _lchk(load().srl_replay_gather(idx.data_ptr(), mb, int(part_len), int(n_steps), int(bool(literal_next)), None, m0.data_ptr(),
-                                   m1.data_ptr(), b0, b1, mem_reward.data_ptr(), mem_terminal.data_ptr(), mem_action.data_ptr(),
-                                   mem_logits.data_ptr(), _ptr(alpha_t), _ptr(beta_t), _ptr(min_logit), s0.data_ptr(), s1.data_ptr(),
-                                   n0.data_ptr(), n1.data_ptr(), act.data_ptr(), rew.data_ptr(), term.data_ptr(), _ptr(w),
-                                   _stream(m0)))
+  call('srl_replay_gather', m0, idx, mb, int(part_len), int(n_steps), int(bool(literal_next)), None, m0, m1, b0, b1, mem_reward,
+       mem_terminal, mem_action, mem_logits, alpha_t, beta_t, min_logit, s0, s1, n0, n1, act, rew, term, w)
   return ((s0, s1), act, rew, (n0, n1), term), w

@@ -14,57 +14,12 @@ the producing kernels (channel slices), the max-pool gradient is routed inside t
 gradients land directly in `p.grad` (views of the DQN's flat gradient bucket — the all-reduce operand).  There is no CPU
 fallback: the class needs the HIP extension.
 """
-import ctypes
-
 import torch
 
 from stackrl_amd import qops
 
 _F = torch.nn.functional
-
-
-def _lib():
-  L = qops.load()
-  if not getattr(L, '_train_conv_ready', False):
-    VP, I32, I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    L.srl_tconv.restype = ctypes.c_int
-    L.srl_tconv.argtypes = [VP, I32, I32, VP, VP, VP, I32, I32] + [I32] * 8 + [VP]
-    L.srl_twrw_scratch_floats.restype = I64
-    L.srl_twrw_scratch_floats.argtypes = [I32] * 6
-    L.srl_twrw.restype = ctypes.c_int
-    L.srl_twrw.argtypes = [VP, I32, I32, VP, VP, VP] + [I32] * 7 + [VP, I32, I32, VP, VP]
-    L.srl_tact_bwd_blocks.restype = I32
-    L.srl_tact_bwd_blocks.argtypes = [I64, I32]
-    L.srl_tact_bwd_scratch_floats.restype = I64
-    L.srl_tact_bwd_scratch_floats.argtypes = [I64, I32]
-    L.srl_tact_bwd.restype = ctypes.c_int
-    L.srl_tact_bwd.argtypes = [VP, I32, I32, VP, I32, I32, VP, VP, VP, VP] + [I32] * 6 + [VP]
-    L.srl_trepack.restype = ctypes.c_int
-    L.srl_trepack.argtypes = [VP, VP, VP, I32, I64, VP]
-    L.srl_thead_fwd.restype = ctypes.c_int
-    L.srl_thead_fwd.argtypes = [VP, VP, VP, VP, VP, I32, I32, VP]
-    L.srl_thead_bwd.restype = ctypes.c_int
-    L.srl_thead_bwd.argtypes = [VP] * 8 + [I32, I32, VP]
-    L.srl_tvalue_fwd.restype = ctypes.c_int
-    L.srl_tvalue_fwd.argtypes = [VP] * 8 + [I32] * 4 + [VP]
-    L.srl_tvalue_bwd.restype = ctypes.c_int
-    L.srl_tvalue_bwd.argtypes = [VP] * 12 + [I32] * 4 + [VP]
-    L.srl_tlayout.restype = ctypes.c_int
-    L.srl_tlayout.argtypes = [VP, I32, I32, VP, I32, I32, I32, I32, VP]
-    L.srl_tcorr_grad.restype = ctypes.c_int
-    L.srl_tcorr_grad.argtypes = [VP, I32, VP, VP, I32, I32, I32, VP]
-    L.srl_tflip.restype = ctypes.c_int
-    L.srl_tflip.argtypes = [VP, VP, I64, I32, VP]
-    L.srl_tu8_to_f32.restype = ctypes.c_int
-    L.srl_tu8_to_f32.argtypes = [VP, VP, I64, VP]
-    L.srl_train_conv_last_error.restype = ctypes.c_char_p
-    L._train_conv_ready = True
-  return L
-
-
-def _chk(rc):
-  if rc:
-    raise RuntimeError(_lib().srl_train_conv_last_error().decode())
+_lib = qops.load      # the library's one loader, under the name this module's callers used before `qops._SIGS` declared every export
 
 
 class Act(object):
@@ -75,9 +30,6 @@ class Act(object):
     self.B, self.H, self.W, self.stride = (int(v) for v in t.shape)
     self.C = int(C) if C is not None else self.stride
     self.off = int(off)
-
-  def ptr(self):
-    return self.t.data_ptr()
 
   def first(self, n):
     """The first n samples (the batch is the outermost dimension)."""
@@ -97,9 +49,7 @@ def tconv(x, wp, bias, cout, taps=9, relu=True, out=None, d2s=0):
     y = Act(torch.empty((B, 2 * H, 2 * W, co) if d2s else (B, H, W, co), dtype=torch.float32, device=x.t.device))
   else:
     y = Act(out[0], co, out[1])
-  with torch.cuda.device(x.t.device):
-    _chk(_lib().srl_tconv(x.ptr(), x.stride, x.off, wp.data_ptr(), None if bias is None else bias.data_ptr(), y.ptr(), y.stride,
-                          y.off, B, H, W, x.C, cout, taps, int(bool(relu)), int(d2s), qops._stream(x.t)))
+  qops.call('srl_tconv', x.t, x.t, x.stride, x.off, wp, bias, y.t, y.stride, y.off, B, H, W, x.C, cout, taps, int(bool(relu)), int(d2s))
   return y
 
 
@@ -130,13 +80,10 @@ def twrw(x, gz, gw, scratch, taps=9, convt=False, bias=None):
   `tact_bwd(..., defer_bias=True)`: the same finishing launch writes the bias gradient."""
   B, H, W = x.B, x.H, x.W
   cout = int(gz.shape[-1])
-  n = _lib().srl_twrw_scratch_floats(B, H, W, x.C, cout, taps)
+  n = qops.load().srl_twrw_scratch_floats(B, H, W, x.C, cout, taps)
   sc = scratch.get('wrw', n, gz.device)
   bp, bn, bc, gb = bias if bias is not None else (None, 0, 0, None)
-  with torch.cuda.device(gz.device):
-    _chk(_lib().srl_twrw(x.ptr(), x.stride, x.off, gz.data_ptr(), gw.data_ptr(), sc.data_ptr(), B, H, W, x.C, cout, taps,
-                         int(bool(convt)), None if bp is None else bp.data_ptr(), int(bn), int(bc),
-                         None if gb is None else gb.data_ptr(), qops._stream(gz)))
+  qops.call('srl_twrw', gz, x.t, x.stride, x.off, gz, gw, sc, B, H, W, x.C, cout, taps, int(bool(convt)), bp, int(bn), int(bc), gb)
 
 
 def tact_bwd(g, y, scratch, gbias=None, gpool=None, relu=True, s2d=False, defer_bias=False):
@@ -145,22 +92,18 @@ def tact_bwd(g, y, scratch, gbias=None, gpool=None, relu=True, s2d=False, defer_
   B, H, W, C = g.B, g.H, g.W, g.C
   dev = g.t.device
   gz = torch.empty((B, H // 2, W // 2, 4 * C) if s2d else (B, H, W, C), dtype=torch.float32, device=dev)
-  sc = scratch.get('act', _lib().srl_tact_bwd_scratch_floats(B * H * W, C), dev) if gbias is not None else None
-  with torch.cuda.device(dev):
-    _chk(_lib().srl_tact_bwd(g.ptr(), g.stride, g.off, None if y is None else y.ptr(), 0 if y is None else y.stride,
-                             0 if y is None else y.off, None if gpool is None else gpool.data_ptr(), gz.data_ptr(),
-                             None if (gbias is None or defer_bias) else gbias.data_ptr(), None if sc is None else sc.data_ptr(),
-                             B, H, W, C, int(bool(relu)), int(bool(s2d)), qops._stream(g.t)))
+  sc = scratch.get('act', qops.load().srl_tact_bwd_scratch_floats(B * H * W, C), dev) if gbias is not None else None
+  qops.call('srl_tact_bwd', g.t, g.t, g.stride, g.off, None if y is None else y.t, 0 if y is None else y.stride, 0 if y is None else y.off,
+            gpool, gz, None if defer_bias else gbias, sc, B, H, W, C, int(bool(relu)), int(bool(s2d)))
   if defer_bias:
-    return gz, (sc, _lib().srl_tact_bwd_blocks(B * H * W, C), C, gbias)
+    return gz, (sc, qops.load().srl_tact_bwd_blocks(B * H * W, C), C, gbias)
   return gz
 
 
 def to_nchw(a):
   """`srl_tlayout`: an `Act` -> contiguous channel-major tensor [B, C, H, W] (what the cross-correlation kernels read)."""
   out = torch.empty((a.B, a.C, a.H, a.W), dtype=torch.float32, device=a.t.device)
-  with torch.cuda.device(a.t.device):
-    _chk(_lib().srl_tlayout(a.ptr(), a.stride, a.off, out.data_ptr(), a.B, a.H * a.W, a.C, 0, qops._stream(a.t)))
+  qops.call('srl_tlayout', a.t, a.t, a.stride, a.off, out, a.B, a.H * a.W, a.C, 0)
   return out
 
 
@@ -168,8 +111,7 @@ def to_nhwc(t):
   """`srl_tlayout`: a contiguous channel-major tensor [B, C, H, W] -> `Act` [B, H, W, C]."""
   B, C, H, W = (int(v) for v in t.shape)
   out = torch.empty((B, H, W, C), dtype=torch.float32, device=t.device)
-  with torch.cuda.device(t.device):
-    _chk(_lib().srl_tlayout(t.data_ptr(), 0, 0, out.data_ptr(), B, H * W, C, 1, qops._stream(t)))
+  qops.call('srl_tlayout', t, t, 0, 0, out, B, H * W, C, 1)
   return Act(out)
 
 
@@ -179,18 +121,14 @@ def input_scale(x):
     return (x.float() / 255.0) if x.dtype == torch.uint8 else x.float().contiguous()
   x = x.contiguous()
   out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-  with torch.cuda.device(x.device):
-    _chk(_lib().srl_tu8_to_f32(x.data_ptr(), out.data_ptr(), x.numel(), qops._stream(x)))
+  qops.call('srl_tu8_to_f32', x, x, out, x.numel())
   return out
 
 
 def pool2x2(y):
   """2 x 2 max-pool of an `Act` (csrc/epilogue.hip) -> contiguous [B, H/2, W/2, C]."""
   out = torch.empty((y.B, y.H // 2, y.W // 2, y.C), dtype=torch.float32, device=y.t.device)
-  with torch.cuda.device(y.t.device):
-    rc = qops.load().srl_pool2x2(y.ptr(), out.data_ptr(), y.B, y.H, y.W, y.C, y.stride, y.off, 1, qops._stream(y.t))
-  if rc:
-    raise RuntimeError(qops.load().srl_epilogue_last_error().decode())
+  qops.call('srl_pool2x2', y.t, y.t, out, y.B, y.H, y.W, y.C, y.stride, y.off, 1)
   return Act(out)
 
 
@@ -248,9 +186,7 @@ class Packed(object):
       with torch.no_grad():
         for w, off in self._own:
           self.flat[off:off + w.numel()].copy_(w.detach().reshape(-1))
-    with torch.cuda.device(self.packed.device):
-      _chk(_lib().srl_trepack(self.flat.data_ptr(), self.packed.data_ptr(), self.desc.data_ptr(), self.nlayers, self.total,
-                              qops._stream(self.packed)))
+    qops.call('srl_trepack', self.packed, self.flat, self.packed, self.desc, self.nlayers, self.total)
 
   def w(self, m, kind):
     o, n = self.view[(m, kind)]
@@ -267,7 +203,7 @@ class HandNet(object):
   def __init__(self, net, flat=None, precision=qops.BF16X3):
     if not next(net.parameters()).is_cuda:
       raise RuntimeError('HandNet needs a HIP device: there is no CPU fallback')
-    _lib()
+    qops.load()
     self.net = net
     self.packed = Packed(net, flat)
     self.scratch = _Scratch()
@@ -393,11 +329,8 @@ class HandNet(object):
     v = torch.empty((B,), dtype=torch.float32, device=xm.device)
     pw, pb = net.pos[4].weight.detach().reshape(-1), net.pos[4].bias.detach()
     q = torch.empty((B, O * O), dtype=torch.float32, device=xm.device)
-    with torch.cuda.device(q.device):
-      _chk(_lib().srl_tvalue_fwd(x0d.data_ptr(), d1.weight.data_ptr(), d1.bias.data_ptr(), d2.weight.data_ptr(), d2.bias.data_ptr(),
-                                 None if pooled is None else pooled.data_ptr(), None if hid is None else hid.data_ptr(),
-                                 v.data_ptr(), B, P, C, U, qops._stream(q)))
-      _chk(_lib().srl_thead_fwd(z2.t.data_ptr(), pw.data_ptr(), pb.data_ptr(), v.data_ptr(), q.data_ptr(), B, O * O, qops._stream(q)))
+    qops.call('srl_tvalue_fwd', q, x0d, d1.weight, d1.bias, d2.weight, d2.bias, pooled, hid, v, B, P, C, U)
+    qops.call('srl_thead_fwd', q, z2.t, pw, pb, v, q, B, O * O)
     if save:
       self.saved = dict(tape_l=tape_l, tape_r=tape_r, fl=fl, fr=fr, xl_n=xl_n, xr_n=xr_n, cin=cin, z1=z1, z2=z2,
                         pooled=pooled, hid=hid, x0=x0, B=B, O=O)
@@ -417,10 +350,8 @@ class HandNet(object):
         p_.grad = torch.zeros_like(p_)
     gz2 = torch.empty((n, O, O, 16), dtype=torch.float32, device=dev)
     gv = torch.empty((n,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-      _chk(_lib().srl_thead_bwd(z2.data_ptr(), pj.weight.detach().reshape(-1).data_ptr(), grad_q.contiguous().data_ptr(),
-                                gz2.data_ptr(), gv.data_ptr(), pj.weight.grad.data_ptr(), pj.bias.grad.data_ptr(),
-                                self.scratch.get('head', 17 * n, dev).data_ptr(), n, A, qops._stream(gz2)))
+    qops.call('srl_thead_bwd', gz2, z2, pj.weight.detach().reshape(-1), grad_q.contiguous(), gz2, gv, pj.weight.grad, pj.bias.grad,
+              self.scratch.get('head', 17 * n, dev), n, A)
     g = self._layer_bwd(net.pos[2], S['z1'], S['z2'], Act(gz2), n)
     g = self._layer_bwd(net.pos[0], S['cin'], S['z1'], g, n)                     # [n, O, O, 16], channel 0 = d / d corr
     kh = int(S['xr_n'].shape[-1])
@@ -430,9 +361,8 @@ class HandNet(object):
     gcorr = torch.empty((n, O, O), dtype=torch.float32, device=dev)
     gp = torch.empty((n, O + 2 * (kh - 1), O + 2 * (kh - 1)), dtype=torch.float32, device=dev)
     wflip = torch.empty((n, C, kh, kh), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-      _chk(_lib().srl_tcorr_grad(g.t.data_ptr(), g.stride, gcorr.data_ptr(), gp.data_ptr(), n, O, kh - 1, qops._stream(gp)))
-      _chk(_lib().srl_tflip(S['xr_n'].data_ptr(), wflip.data_ptr(), n * C, kh * kh, qops._stream(gp)))
+    qops.call('srl_tcorr_grad', gp, g.t, g.stride, gcorr, gp, n, O, kh - 1)
+    qops.call('srl_tflip', gp, S['xr_n'], wflip, n * C, kh * kh)
     dxl = qops._xcorr_mfma(1, self.precision, gp, wflip, n, C, H, kh)                           # [n, C, H, H]
     dxr = qops._xcorr_mfma(2, self.precision, S['xl_n'][:n], gcorr, n, C, H, kh)              # [n, C, kh, kh]
     g_l, g_r = to_nhwc(dxl), to_nhwc(dxr)
@@ -444,11 +374,8 @@ class HandNet(object):
       Cb, U, P = int(d1.in_features), int(d1.out_features), x0.H * x0.W
       gin = g_dec.dense()
       gx = torch.empty((n, x0.H, x0.W, Cb), dtype=torch.float32, device=dev)
-      with torch.cuda.device(dev):
-        _chk(_lib().srl_tvalue_bwd(gv.data_ptr(), S['hid'].data_ptr(), S['pooled'].data_ptr(), d1.weight.data_ptr(),
-                                   d2.weight.data_ptr(), gin.data_ptr(), gx.data_ptr(), d1.weight.grad.data_ptr(),
-                                   d1.bias.grad.data_ptr(), d2.weight.grad.data_ptr(), d2.bias.grad.data_ptr(),
-                                   self.scratch.get('value', n * U, dev).data_ptr(), n, P, Cb, U, qops._stream(gx)))
+      qops.call('srl_tvalue_bwd', gx, gv, S['hid'], S['pooled'], d1.weight, d2.weight, gin, gx, d1.weight.grad, d1.bias.grad, d2.weight.grad,
+                d2.bias.grad, self.scratch.get('value', n * U, dev), n, P, Cb, U)
       return Act(gx)
 
     self._unet_bwd(net.left, S['tape_l'], g_l, value_branch, n)

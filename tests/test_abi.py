@@ -43,6 +43,72 @@ def test_qnet_library_exports_every_declared_symbol():
     assert hasattr(L, n), 'missing export ' + n
 
 
+QNET_HEADERS = ('stackrl_qnet.h', 'stackrl_explore.h', 'stackrl_greedy.h', 'stackrl_baseline_rows.h')
+
+
+def _qnet_declarations():
+  """name -> (return type, [parameter declarations]) of every `ret name(params);` of the four Q-net headers, comments and
+  preprocessor lines stripped."""
+  out = {}
+  for h in QNET_HEADERS:
+    with open(os.path.join(ROOT, 'include', h)) as f:
+      txt = f.read()
+    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
+    txt = re.sub(r'//[^\n]*', '', txt)
+    txt = re.sub(r'^\s*#[^\n]*', '', txt, flags=re.M).replace('extern "C" {', '')
+    for ret, name, params in re.findall(r'([A-Za-z_][\w\s\*]*?)\b(srl_\w+)\s*\(([^)]*)\)\s*;', txt):
+      assert name not in out, name + ' is declared twice'
+      params = [' '.join(p.split()) for p in params.split(',')]
+      out[name] = (' '.join(ret.split()), [] if params == ['void'] else params)
+  return out
+
+
+def _ctype(decl, ret=False):
+  """The ctypes type of a return type or a parameter declaration: any pointer is void*, but a returned const char* a string."""
+  if '*' in decl:
+    return ctypes.c_char_p if ret and decl.replace(' ', '') == 'constchar*' else ctypes.c_void_p
+  base = [t for t in decl.split() if t != 'const'][0]
+  return {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'double': ctypes.c_double, 'int': ctypes.c_int}[base]
+
+
+def test_qnet_signature_table_matches_the_headers():
+  """`qops._SIGS` names exactly the exports the four headers declare, each with the declaration's return and argument types."""
+  from stackrl_amd import qops
+  decl = _qnet_declarations()
+  assert len(decl) == 67
+  assert sorted(qops._SIGS) == sorted(decl)
+  for name, (ret, params) in decl.items():
+    res, args, _ = qops._SIGS[name]
+    assert res is _ctype(ret, ret=True), name
+    assert list(args) == [_ctype(p) for p in params], name
+    if ret == 'int':               # the launching exports: the stream goes last (what `qops.call` appends)
+      assert params[-1].replace(' ', '') == 'void*stream', name
+
+
+def test_qnet_error_accessors_match_the_sources():
+  """Every .hip file keeps its own error text: the accessor the table names for an export is the one of the file that defines
+  the export (qnet.hip, greedy.hip and heuristics.hip share `srl_qnet_last_error` through `srl_qnet_set_error`)."""
+  from stackrl_amd import build, qops
+  where, launches = {}, {}
+  for f in build.QSRC:
+    with open(os.path.join(build.CSRC, f)) as fh:
+      for ret, name in re.findall(r'^(const char\*|int|int32_t|int64_t)\s+(srl_\w+)\s*\(', fh.read(), re.M):
+        assert name not in where, name + ' is defined twice'
+        where[name] = f
+        launches[name] = ret == 'int'    # status returns; the size and support queries return int32_t / int64_t
+  assert len(where) == 67 and len(set(where.values())) == 9
+  assert sorted(where) == sorted(qops._SIGS)
+  own = {f: [n for n, g in where.items() if g == f and n.endswith('_last_error')] for f in build.QSRC}
+  assert all(len(v) == 1 for f, v in own.items() if f not in ('greedy.hip', 'heuristics.hip')), own
+  for f in ('greedy.hip', 'heuristics.hip'):
+    with open(os.path.join(build.CSRC, f)) as fh:
+      assert own[f] == [] and 'srl_qnet_set_error' in fh.read()
+    own[f] = own['qnet.hip']
+  assert len({v[0] for v in own.values()}) == 7
+  for name, (_, _, err) in qops._SIGS.items():
+    assert err == (own[where[name]][0] if launches[name] else None), name
+
+
 def test_config_struct_matches_header():
   from stackrl_amd.config import CConfig, StackConfig
   with open(os.path.join(ROOT, 'include', 'srl_types.h')) as f:

@@ -50,7 +50,7 @@ def _rows_call(torch, Bd, method, xm, xo, n_valid, dexp=2, wexp=2, localized=0, 
   OH = H - h + 1
   vals = torch.full((B, G, OH, OH), SENT, dtype=torch.float64, device='cuda')
   mask = torch.full((B, G, OH, OH), MSENT, dtype=torch.uint8, device='cuda')
-  rc = Bd._lib().srl_heuristic_rows(Bd.METHODS[method], xm.data_ptr(), xo.data_ptr(), vals.data_ptr(), mask.data_ptr(), B, G, n_valid,
+  rc = Bd.qops.load().srl_heuristic_rows(Bd.METHODS[method], xm.data_ptr(), xo.data_ptr(), vals.data_ptr(), mask.data_ptr(), B, G, n_valid,
                                     H, h, dexp, wexp, localized, threshold, _stream(torch))
   torch.cuda.synchronize()
   return rc, vals, mask
@@ -62,7 +62,7 @@ def _select_call(torch, Bd, vals, mask, goal, minorder, n_valid):
   actions = torch.full((B,), -5, dtype=torch.int64, device='cuda')
   chosen = torch.full((B, G), SENT, dtype=torch.float64, device='cuda')
   neg = torch.full(tuple(vals.shape), SENT, dtype=torch.float64, device='cuda')
-  rc = Bd._lib().srl_baseline_rows_select(vals.data_ptr(), mask.data_ptr() if mask is not None else None, int(goal), minorder, B, G,
+  rc = Bd.qops.load().srl_baseline_rows_select(vals.data_ptr(), mask.data_ptr() if mask is not None else None, int(goal), minorder, B, G,
                                           n_valid, OH, actions.data_ptr(), chosen.data_ptr(), neg.data_ptr(), _stream(torch))
   torch.cuda.synchronize()
   return rc, actions, chosen, neg
@@ -216,7 +216,7 @@ def test_refusals_launch_nothing():
   torch = pytest.importorskip('torch')
   from stackrl_amd import baselines as Bd
   xm, xo = _dev(torch, *_obs(32, 8, 2, 3))
-  L = Bd._lib()
+  L = Bd.qops.load()
   for bad in (0, 4, -1):
     rc, vals, mask = _rows_call(torch, Bd, 'height', xm, xo, bad)
     assert rc == 1 and b'srl_heuristic_rows: bad arguments' in L.srl_qnet_last_error()

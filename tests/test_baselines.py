@@ -371,7 +371,7 @@ def test_map_larger_than_lds_is_refused_before_launch():
     Bd.heuristic_values('height', (xm, xo))
   vals = torch.full((2, 193, 193), -7.0, dtype=torch.float64, device='cuda')
   mask = torch.full((2, 193, 193), 9, dtype=torch.uint8, device='cuda')
-  L = Bd._lib()
+  L = Bd.qops.load()
   rc = L.srl_heuristic(2, xm.data_ptr(), xo.data_ptr(), vals.data_ptr(), mask.data_ptr(), 2, 256, 64, 2, 2, 0, 0.75,
                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
   torch.cuda.synchronize()

@@ -91,7 +91,7 @@ def test_xcorr_mfma_at_the_update_batch_sizes_matches_torch_fp64(B, C, H, h, pre
   library formulation with autograd in float64.  Tolerances as stated above; the inputs are non-negative maps and kernels
   of mixed sign, so that a wrong or missing channel shows as an error of the order of the tensor's scale."""
   from stackrl_amd import nets, qops, qtrain
-  L = qtrain._lib()
+  L = qops.load()
   monkeypatch.setenv('SRL_XCORR_ROWS', '0')            # the Toeplitz kernel, whatever the batch size
   g = torch.Generator(device='cuda').manual_seed(B * 13 + C + precision)
   O = H - h + 1

@@ -272,7 +272,7 @@ def test_value_branch_forward_and_gradients_match_torch_fp64(B, n, P, C, U):
   """`layers.value` (layers.py:424-436): average pool -> Dense + ReLU -> Dense(1), forward and — for the first n samples — the
   gradients of both dense layers and of the bottom features (added to an incoming gradient), against float64 on the host."""
   from stackrl_amd import qtrain, qops
-  L = qtrain._lib()
+  L = qops.load()
   g = torch.Generator(device='cuda').manual_seed(B + C)
   side = int(round(P ** 0.5))
   x0 = torch.randn((B, side, side, C), generator=g, device='cuda')
@@ -310,7 +310,7 @@ def test_layout_passes_are_exact():
   """The copies around the cross-correlation (channels-last <-> channel-major, channel 0 of a gradient plain and zero-padded,
   flipped kernels) and the uint8 -> float32 / 255 input scaling, against the framework formulations, bit for bit."""
   from stackrl_amd import qtrain, qops
-  L = qtrain._lib()
+  L = qops.load()
   g = torch.Generator(device='cuda').manual_seed(4)
   buf = torch.randn((3, 9, 7, 24), generator=g, device='cuda')
   a = qtrain.Act(buf, 16, 4)
