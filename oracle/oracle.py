@@ -63,10 +63,13 @@ class OracleEnv(object):
     if seed is not None:
       self.seed(seed)
 
-  def __del__(self):
+  def close(self):
     if getattr(self, 'h', None):
       self.L.srlo_destroy(self.h)
       self.h = None
+
+  def __del__(self):
+    self.close()
 
   def seed(self, seed):
     self.L.srlo_seed(self.h, ctypes.c_uint32(seed % 2**32))
