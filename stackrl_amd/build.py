@@ -136,6 +136,17 @@ def qstale():
   return i is None or i['hash'] != source_hash(QDEPS, QFLAGS)
 
 
+# the policy-comparison statistics (include/stackrl_compare.h): a library of its own, so that libstackrl_qnet.so keeps its exports
+CLIB = os.path.join(HERE, 'libstackrl_compare.so')
+CSRCS = ['compare.hip']
+CDEPS = CSRCS + [os.path.join('..', '..', 'include', 'stackrl_compare.h')]
+
+
+def cstale():
+  i = info(CLIB)
+  return i is None or i['hash'] != source_hash(CDEPS, QFLAGS)
+
+
 def build(force=False, verbose=False):
   hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
   if force or stale():
@@ -151,6 +162,11 @@ def build(force=False, verbose=False):
       subprocess.check_call(cmd)
   if force or qstale():
     cmd = [hipcc] + QFLAGS + [_info_flag('no-slp', source_hash(QDEPS, QFLAGS))] + [os.path.join(CSRC, f) for f in QSRC] + ['-o', QLIB]
+    if verbose:
+      print(' '.join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+  if force or cstale():
+    cmd = [hipcc] + QFLAGS + [_info_flag('no-slp', source_hash(CDEPS, QFLAGS))] + [os.path.join(CSRC, f) for f in CSRCS] + ['-o', CLIB]
     if verbose:
       print(' '.join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)
