@@ -17,12 +17,11 @@ import os
 import numpy as np
 import torch
 
-from stackrl_amd import build as _build
+from stackrl_amd import _bind
 
 MAX_POLICIES = 8
 HOLD = -2          # SRL_ACTION_HOLD (include/srl_types.h): the env sits a call out
 
-_LIB = None
 _VP, _I32, _INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int
 # export -> (restype, argtypes, error accessor or None): every declaration of include/stackrl_compare.h (pointers as void*);
 # tests/test_compare_abi.py holds the table to the header and the library.  The launching export returns int and takes the
@@ -35,30 +34,7 @@ _SIGS = {
 }
 
 
-def load():
-  """Load (building first if the library is missing) and return the ctypes library; a symbol of `_SIGS` it lacks fails here."""
-  global _LIB
-  if _LIB is None:
-    if not os.path.isfile(_build.CLIB):
-      _build.build()
-    lib = ctypes.CDLL(_build.CLIB)
-    for name, (res, args, _) in _SIGS.items():
-      fn = getattr(lib, name)
-      fn.restype = res
-      fn.argtypes = args
-    _LIB = lib
-  return _LIB
-
-
-def call(name, t, *args):
-  """One launch of the export `name` on the device and current stream of tensor `t`: tensors among `args` go as their data
-  pointers, None as NULL, the stream last; a non-zero return raises RuntimeError with the text of the export's error accessor."""
-  lib = load()
-  with torch.cuda.device(t.device):
-    rc = getattr(lib, name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
-                            ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream))
-  if rc:
-    raise RuntimeError(getattr(lib, _SIGS[name][2])().decode())
+load, call = _bind.binding('compare', _SIGS)
 
 
 # ------------------------------------------------------------------------------------------------ the record

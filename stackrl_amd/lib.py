@@ -1,12 +1,10 @@
-"""ctypes loader of libstackrl_hip.so (include/stackrl_hip.h).  There is no CPU fallback: if the HIP
-library is missing or cannot be loaded the import of the product path fails loudly."""
+"""ctypes loader of libstackrl_hip.so (include/stackrl_hip.h): `load` builds first if the library is missing and returns the
+ctypes library.  There is no CPU fallback: if the HIP library is missing or cannot be loaded the import of the product path
+fails loudly."""
 import ctypes
-import os
 
-from stackrl_amd import build as _build
+from stackrl_amd import _bind, build as _build
 from stackrl_amd.config import CConfig
-
-_LIB = None
 
 _VP = ctypes.c_void_p
 _SIGS = {
@@ -44,23 +42,11 @@ _SIGS = {
 EXPORTS = tuple(sorted(_SIGS))
 
 
+load, _ = _bind.binding('env', _SIGS)      # the handle API reports its errors per call (env.py `_check`), not through `call`
+
+
 def path():
-  return _build.LIB
-
-
-def load():
-  """Load (building first if the sources are newer) and return the ctypes library."""
-  global _LIB
-  if _LIB is None:
-    if not os.path.isfile(_build.LIB):
-      _build.build()
-    lib = ctypes.CDLL(_build.LIB)
-    for name, (res, args) in _SIGS.items():
-      fn = getattr(lib, name)  # AttributeError = symbol missing: fail loudly
-      fn.restype = res
-      fn.argtypes = args
-    _LIB = lib
-  return _LIB
+  return _build.LIBRARIES['env'].path
 
 
 def last_error():

@@ -1,15 +1,12 @@
 """Python side of libstackrl_qnet.so (include/stackrl_qnet.h, stackrl_explore.h, stackrl_greedy.h, stackrl_baseline_rows.h): the one
-signature table (`_SIGS`), loader (`load`) and checked launch (`call`) of the library, which qtrain.py and baselines.py use too,
-and the hand-written ops of the Q-net rollout path.
+signature table (`_SIGS`) of the library, its loader (`load`) and checked launch (`call`, both from _bind.py), which qtrain.py
+and baselines.py use too, and the hand-written ops of the Q-net rollout path.
 No CPU fallback: these functions need a HIP device and the built library."""
 import ctypes
-import os
 
 import torch
 
-from stackrl_amd import build as _build
-
-_LIB = None
+from stackrl_amd import _bind
 
 _VP, _I32, _I64, _F32, _F64, _INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_int
 # every .hip file keeps the text of its last refusal in a buffer of its own: the accessor that goes with an export is the one
@@ -98,34 +95,8 @@ _SIGS = {
 }
 
 
-def load():
-  """Load (building first if the library is missing) and return the ctypes library; a symbol of `_SIGS` it lacks fails here."""
-  global _LIB
-  if _LIB is None:
-    if not os.path.isfile(_build.QLIB):
-      _build.build()
-    lib = ctypes.CDLL(_build.QLIB)
-    for name, (res, args, _) in _SIGS.items():
-      fn = getattr(lib, name)  # AttributeError = symbol missing: fail loudly
-      fn.restype = res
-      fn.argtypes = args
-    _LIB = lib
-  return _LIB
-
-
-def _stream(t):
-  return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def call(name, t, *args):
-  """One launch of the export `name` on the device and current stream of tensor `t`: tensors among `args` go as their
-  data pointers, None as NULL, the stream last; a non-zero return raises RuntimeError with the text of the export's own
-  error accessor (`_SIGS`)."""
-  lib = load()
-  with torch.cuda.device(t.device):
-    rc = getattr(lib, name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], _stream(t))
-  if rc:
-    raise RuntimeError(getattr(lib, _SIGS[name][2])().decode())
+load, call = _bind.binding('qnet', _SIGS)
+_stream = _bind.stream
 
 
 _SCRATCH = {}

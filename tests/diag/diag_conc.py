@@ -6,12 +6,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import numpy as np, torch
 if os.environ.get('SRL_DIAG_LIB'):      # run against another build of libstackrl_hip.so (diagnostic variants)
   from stackrl_amd import build as _b
-  _b.LIB = os.path.abspath(os.environ['SRL_DIAG_LIB'])
-  _b.stale = lambda: False
+  _b.LIBRARIES['env'].path = os.path.abspath(os.environ['SRL_DIAG_LIB'])
 if os.environ.get('SRL_DIAG_QLIB'):     # ... and of libstackrl_qnet.so
   from stackrl_amd import build as _b
-  _b.QLIB = os.path.abspath(os.environ['SRL_DIAG_QLIB'])
-  _b.qstale = lambda: False
+  _b.LIBRARIES['qnet'].path = os.path.abspath(os.environ['SRL_DIAG_QLIB'])
 from stackrl_amd import assets, env as envs, nets, qops
 from stackrl_amd.config import StackConfig
 from oracle import oracle

@@ -167,4 +167,4 @@ def test_qnet_library_exports_the_row_entry_points():
   L = ctypes.CDLL(build.QLIB)
   for n in names:
     assert hasattr(L, n), 'missing export ' + n
-  assert any(d.endswith('stackrl_baseline_rows.h') for d in build.QDEPS)
+  assert any(d.endswith('stackrl_baseline_rows.h') for d in build.deps('qnet'))

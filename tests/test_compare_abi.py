@@ -53,25 +53,25 @@ def test_header_table_and_exports_agree():
   # defined once, in the library's one source file
   with open(os.path.join(build.CSRC, 'compare.hip')) as f:
     defined = re.findall(r'^(?:const char\*|int|int32_t)\s+(srl_\w+)\s*\(', f.read(), re.M)
-  assert sorted(defined) == sorted(decl) and build.CSRCS == ['compare.hip']
+  assert sorted(defined) == sorted(decl) and build.LIBRARIES['compare'].sources == ['compare.hip']
   lib = compare.load()
   for P in range(0, 10):
     assert lib.srl_compare_record_doubles(P) == (compare.record_doubles(P) if 1 <= P <= 8 else 0)
   assert compare.record_doubles(8) == 189 and compare.MAX_POLICIES == 8
   # the other libraries are what they were
-  assert 'compare.hip' not in build.QSRC and not any('compare' in d for d in build.QDEPS)
+  assert 'compare.hip' not in build.QSRC and not any('compare' in d for d in build.deps('qnet'))
 
 
 def test_library_carries_the_hash_of_its_sources():
   from stackrl_amd import compare
   build.build()                                   # a no-op unless a library is missing or stale
   i = build.info(build.CLIB)
-  assert i is not None and i['variant'] == 'no-slp' and i['hash'] == build.source_hash(build.CDEPS, build.QFLAGS)
-  assert not build.cstale()
+  assert i is not None and i['variant'] == 'no-slp' and i['hash'] == build.source_hash('compare')
+  assert not build.stale('compare')
   assert compare.load().srl_compare_build_info().decode() == 'SRL_BUILD_INFO<no-slp|{}>'.format(i['hash'])
-  assert '-fno-slp-vectorize' in build.QFLAGS
-  # the hash follows the header and the source
-  assert os.path.join('..', '..', 'include', 'stackrl_compare.h') in build.CDEPS and 'compare.hip' in build.CDEPS
+  assert '-fno-slp-vectorize' in build.LIBRARIES['compare'].flags
+  # the hash follows the header and the source: the set derived from the source's includes is exactly these two
+  assert build.deps('compare') == [os.path.join('include', 'stackrl_compare.h'), os.path.join('stackrl_amd', 'csrc', 'compare.hip')]
 
 
 def test_no_kernel_of_the_library_contains_the_flagged_packed_form():

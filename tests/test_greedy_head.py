@@ -24,7 +24,7 @@ def test_qnet_library_exports_the_greedy_head():
   L = ctypes.CDLL(build.QLIB)
   for n in names:
     assert hasattr(L, n), 'missing export ' + n
-  assert 'greedy.hip' in build.QSRC and any(d.endswith('stackrl_greedy.h') for d in build.QDEPS)
+  assert 'greedy.hip' in build.QSRC and any(d.endswith('stackrl_greedy.h') for d in build.deps('qnet'))
 
 
 @pytest.mark.parametrize('B,G,n_valid,A', [(1, 1, 1, 1), (3, 1, 1, 7), (4, 2, 1, 33), (4, 2, 2, 33), (2, 8, 7, 300)])

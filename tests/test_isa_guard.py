@@ -1,4 +1,4 @@
-"""No kernel of either library may contain the packed-fp32 instruction form that misreads an operand on gfx950.
+"""No kernel of any library may contain the packed-fp32 instruction form that misreads an operand on gfx950.
 
 Found in round 3, its trigger narrowed down in round 4 (tools/experiments/pk_seq2.hip is the 30-line
 victim, tools/experiments/pk_aggressor.hip the one-property aggressors): a packed-fp32 instruction whose LOW lane takes the HIGH
@@ -8,7 +8,7 @@ gfx950's 128-bit-operand MFMA shapes (`v_mfma_f32_16x16x32_bf16` / `_f16`, `_32x
 10,000 beside the Q-net's bf16 convolution kernels), and never alone, beside fp32 or 64-bit-operand MFMAs, or beside vector-ALU
 work.  clang's SLP vectoriser emits the form.  The env library is compiled with the vectoriser and a pass over its assembly
 that swaps the two (commuting) sources of every such instruction (stackrl_amd/isa_fix.py; the same selection on the first
-source is clean); the Q-net library is built without the vectoriser.  These tests compile every source to gfx950 assembly
+source is clean); the other libraries are built without the vectoriser.  These tests compile every source to gfx950 assembly
 the way stackrl_amd/build.py does AND take the shipped .so files apart (no GPU needed), so that a later flag, compiler or
 source change — or a stale library — cannot bring the form back unnoticed."""
 import os
@@ -21,12 +21,16 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 
 
 def test_no_kernel_contains_the_packed_form_that_fails_beside_wide_operand_mfma_wavefronts():
+  env = build.LIBRARIES['env']
   jobs = [lambda: build.fixed_env_asm(HIPCC)[0],                                                      # the product's env library
-          lambda: build.device_asm(HIPCC, build.FLAGS_SAFE, os.path.join(build.CSRC, build.SOURCES[0]))]   # and its fall-back build
-  jobs += [(lambda s=s: build.device_asm(HIPCC, build.QFLAGS, os.path.join(build.CSRC, s))) for s in build.QSRC]
+          lambda: build.device_asm(HIPCC, build.FLAGS_SAFE, os.path.join(build.CSRC, env.sources[0]))]     # and its fall-back build
+  names = ['env (vectorised + rewritten)', 'env (fall-back)']
+  for lib in build.LIBRARIES.values():             # every other library: each source, the way its one command compiles it
+    if lib is not env:
+      jobs += [(lambda s=s, lib=lib: build.device_asm(HIPCC, lib.flags, os.path.join(build.CSRC, s))) for s in lib.sources]
+      names += lib.sources
   with ThreadPoolExecutor(max_workers=6) as ex:
     texts = list(ex.map(lambda f: f(), jobs))
-  names = ['env (vectorised + rewritten)', 'env (fall-back)'] + build.QSRC
   for name, text in zip(names, texts):
     hits = isa_fix.flagged(text)
     assert not hits, '{}: packed instructions that take the high half of their second source for the low lane: {}'.format(name, hits[:5])
@@ -35,31 +39,37 @@ def test_no_kernel_contains_the_packed_form_that_fails_beside_wide_operand_mfma_
   assert texts[0].count('v_pk_') > 1000 and texts[1].count('v_pk_') > 50
 
 
+# "the scan saw real code", per library: (disassembly of every code object, variant) -> bool
+_SAW = {
+  # the env kernels: packed instructions by the hundred, the step kernel by name
+  'env': lambda texts, variant: sum(t.count('v_pk_') for t in texts) > (1000 if variant == build.VARIANT_FIXED else 50) and
+                                any('<srl_k_step>:' in t for t in texts) and any('<srl_k_render>:' in t for t in texts),
+  'qnet': lambda texts, variant: sum(t.count('v_mfma_') for t in texts) > 1000,
+  'compare': lambda texts, variant: sum(t.count('k_compare') for t in texts) >= 8,
+}
+
+
 def test_the_shipped_libraries_are_built_from_these_sources_and_contain_no_flagged_instruction():
-  """The ARTEFACTS, not the recipe: the two .so files that travel to the GPU box are taken apart (`.hip_fatbin` section ->
+  """The ARTEFACTS, not the recipe: every .so file that travels to the GPU box is taken apart (`.hip_fatbin` section ->
   the gfx950 code object of every translation unit -> llvm-objdump) and scanned; the hash each carries (`srl_build_info`)
   must be that of the sources and flags in the tree, so a stale or hand-copied library fails here; and the env library
   says which variant it is (the bench line prints it)."""
   build.build()                                   # a no-op unless a library is missing or stale
-  for lib, deps, flags, variants in ((build.LIB, build.DEPS, build.FLAGS, (build.VARIANT_FIXED, build.VARIANT_SAFE)),
-                                     (build.QLIB, build.QDEPS, build.QFLAGS, ('no-slp',))):
-    i = build.info(lib)
-    assert i is not None and i['hash'] == build.source_hash(deps, flags), '{} was not built from the sources in the tree'.format(lib)
-    assert i['variant'] in variants
-    texts = isa_fix.shipped_asm(lib)
-    assert len(texts) == (1 if lib == build.LIB else len(build.QSRC))
+  assert sorted(_SAW) == sorted(build.LIBRARIES)  # a new library comes with its own "saw real code" count
+  for name, lib in build.LIBRARIES.items():
+    i = build.info(lib.path)
+    assert i is not None and i['hash'] == build.source_hash(name), '{} was not built from the sources in the tree'.format(lib.path)
+    assert i['variant'] in lib.variants
+    texts = isa_fix.shipped_asm(lib.path)
+    assert len(texts) == len(lib.sources)
     for t in texts:
       hits = isa_fix.flagged(t)
-      assert not hits, '{}: {}'.format(os.path.basename(lib), hits[:5])
-    if lib == build.LIB:        # the scan saw the env kernels: packed instructions by the hundred, the step kernel by name
-      assert sum(t.count('v_pk_') for t in texts) > (1000 if i['variant'] == build.VARIANT_FIXED else 50)
-      assert any('<srl_k_step>:' in t for t in texts) and any('<srl_k_render>:' in t for t in texts)
-    else:
-      assert sum(t.count('v_mfma_') for t in texts) > 1000
+      assert not hits, '{}: {}'.format(os.path.basename(lib.path), hits[:5])
+    assert _SAW[name](texts, i['variant']), name
 
 
 def test_the_vectoriser_does_emit_the_form_and_the_pass_removes_all_of_it():
-  raw = build.device_asm(HIPCC, build.FLAGS, os.path.join(build.CSRC, build.SOURCES[0]))
+  raw = build.device_asm(HIPCC, build.FLAGS, os.path.join(build.CSRC, build.LIBRARIES['env'].sources[0]))
   assert len(isa_fix.flagged(raw)) > 100          # (955 with the compiler of this image)
   text, n, left = isa_fix.rewrite(raw)
   assert n == len(isa_fix.flagged(raw)) and left == 0 and not isa_fix.flagged(text)

@@ -6,7 +6,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get('SRL_DIAG_QLIB'):
   from stackrl_amd import build as _b
-  _b.QLIB = os.path.abspath(os.environ['SRL_DIAG_QLIB']); _b.qstale = lambda: False
+  _b.LIBRARIES['qnet'].path = os.path.abspath(os.environ['SRL_DIAG_QLIB'])
 import numpy as np, torch
 from stackrl_amd import assets, env as envs, nets, qops, qtrain
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 40

@@ -21,7 +21,7 @@ import torch
 
 if os.environ.get('SRL_DIAG_LIB'):
   from stackrl_amd import build as _b
-  _b.LIB = os.path.abspath(os.environ['SRL_DIAG_LIB'])
+  _b.LIBRARIES['env'].path = os.path.abspath(os.environ['SRL_DIAG_LIB'])
 
 from stackrl_amd import assets, env as envs, nets, qops
 from stackrl_amd.dqn import DQN, PolynomialDecay

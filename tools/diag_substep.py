@@ -5,7 +5,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get('SRL_DIAG_LIB'):
   from stackrl_amd import build as _b
-  _b.LIB = os.path.abspath(os.environ['SRL_DIAG_LIB']); _b.stale = lambda: False
+  _b.LIBRARIES['env'].path = os.path.abspath(os.environ['SRL_DIAG_LIB'])
 import numpy as np, torch
 from stackrl_amd import assets, env as envs, nets, qops
 B, L, N = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])

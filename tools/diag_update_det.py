@@ -6,7 +6,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get('SRL_DIAG_QLIB'):
   from stackrl_amd import build as _b
-  _b.QLIB = os.path.abspath(os.environ['SRL_DIAG_QLIB']); _b.qstale = lambda: False
+  _b.LIBRARIES['qnet'].path = os.path.abspath(os.environ['SRL_DIAG_QLIB'])
 import torch
 from stackrl_amd import assets, env as envs, nets, qops
 from stackrl_amd.dqn import DQN, PolynomialDecay

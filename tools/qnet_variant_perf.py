@@ -2,7 +2,7 @@ import os, sys, time
 sys.path.insert(0, os.getcwd())
 from stackrl_amd import build as b
 if len(sys.argv) > 1 and sys.argv[1] != 'product':
-  b.QLIB = os.path.abspath(sys.argv[1]); b.qstale = lambda: False
+  b.LIBRARIES['qnet'].path = os.path.abspath(sys.argv[1])
 import torch
 from stackrl_amd import nets, qops
 net = nets.DeepQSiamFCN(seed=2).cuda()
