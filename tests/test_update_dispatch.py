@@ -14,7 +14,8 @@ This module
     channels per workgroup has no export: profiles/update_batch_tests_kernel_names.txt is the kernel-name summary of a
     traced run of the update-path GPU tests, with k_tconv at COT 1, 2 and 4 for both tap counts;
   * enumerates the regimes of the product's update (every layer of `DeepQSiamFCN` for the Stack-v0 shapes and the 64 x 64
-    configuration, the three cross-correlation modes in both precisions) and the regimes the parameter lists of the GPU
+    configuration, the three cross-correlation modes in both precisions and with the operand pairs float32 and bf16 features
+    give them, the rollout's forward at a policy chunk of 256 samples) and the regimes the parameter lists of the GPU
     tests reach — imported from the GPU test modules, so that the two cannot drift apart — and asserts that the second set
     contains the first, and the ragged channel splits besides."""
 import ctypes
@@ -27,6 +28,7 @@ torch = pytest.importorskip('torch')        # the GPU test modules import it at 
 
 import test_learner_gpu as TL               # noqa: E402  (parameter lists only; nothing in them runs at import)
 import test_train_conv_gpu as TC            # noqa: E402
+import test_xcorr_exact_gpu as TX           # noqa: E402
 
 
 def conv_case_regimes(cin, cout, B, H, W):
@@ -60,9 +62,35 @@ def xcorr_case_regimes(B, C, H, h, precision, force=None):
   return {D.xcorr_regime(m, precision, B, C, H, h, force=force) for m in (0, 1, 2)}
 
 
-def regimes_reached(conv=None, convt=None, act=None, hand=None, xc_auto=None, xc_update=None):
-  """The regimes the GPU suite reaches with the given parameter lists (default: the lists of the GPU test modules)."""
+ROWS_KIND = {'f32x3': (1, (D.F32, D.F32)), 'f32': (0, (D.F32, D.F32)), 'bf16': (0, (D.BF16, D.BF16))}
+
+
+def xcorr_exact_regimes():
+  """tests/test_xcorr_exact_gpu.py, from its parameter lists: the Toeplitz kernel forced (SRL_XCORR_ROWS=0) in three modes with
+  every operand pair at precision 0 and with the split, the forward at 256 samples, the row-product kernel forced at 3 samples
+  and chosen at 192, and the autograd function under bf16 features."""
   out = set()
+  for H, h in TX.GEOMETRIES:
+    for B, C in TX.TOEPLITZ_BC:
+      out |= {D.xcorr_regime(m, 0, B, C, H, h, (D.F32 if a == 'f32' else D.BF16, D.F32 if k == 'f32' else D.BF16), force='0')
+              for m in (0, 1, 2) for a, k in TX.PAIRS}
+    for B, C in TX.SPLIT_BC:
+      out |= xcorr_case_regimes(B, C, H, h, 1, force='0')
+    for kind in TX.ROWS_KINDS:
+      precision, pair = ROWS_KIND[kind]
+      out.add(D.xcorr_regime(0, precision, TX.LARGE_BATCH, 16, H, h, pair, force='0'))
+    pairs = D.backward_pairs(D.BF16)
+    out |= {D.xcorr_regime(m, 0, 3, 16, H, h, pairs[m], force='0') for m in (0, 1, 2)}
+  for kind in TX.ROWS_KINDS:
+    precision, pair = ROWS_KIND[kind]
+    out |= {D.xcorr_regime(0, precision, 3, C, 128, 32, pair, force='1') for C in TX.ROWS_CHANNELS}
+    out.add(D.xcorr_regime(0, precision, TX.ROWS_BATCH, 16, 128, 32, pair))
+  return out
+
+
+def regimes_reached(conv=None, convt=None, act=None, hand=None, xc_auto=None, xc_update=None, xc_exact=True):
+  """The regimes the GPU suite reaches with the given parameter lists (default: the lists of the GPU test modules)."""
+  out = xcorr_exact_regimes() if xc_exact else set()
   for c in TC.CONV3X3_CASES if conv is None else conv:
     out |= conv_case_regimes(*c)
   for c in TC.CONVT_CASES if convt is None else convt:
@@ -77,9 +105,9 @@ def regimes_reached(conv=None, convt=None, act=None, hand=None, xc_auto=None, xc
     for c in TL.XCORR_UPDATE_CASES if xc_update is None else xc_update:
       out |= xcorr_case_regimes(*c, precision=precision, force='0')       # that test sets SRL_XCORR_ROWS=0
   for B, C, dt in TL.XCORR_ROWS_CASES:      # test_xcorr_row_product_forward: forced for small batches, then the Toeplitz kernel forced
-    precision, f32 = {'f32x3': (1, True), 'f32': (0, True), 'bf16': (0, False)}[dt]
-    out.add(D.xcorr_regime(0, precision, B, C, 128, 32, f32=f32, force=None if B >= 192 else '1'))
-    out.add(D.xcorr_regime(0, precision, B, C, 128, 32, f32=f32, force='0'))
+    precision, pair = ROWS_KIND[dt]
+    out.add(D.xcorr_regime(0, precision, B, C, 128, 32, pair, force=None if B >= 192 else '1'))
+    out.add(D.xcorr_regime(0, precision, B, C, 128, 32, pair, force='0'))
   return out
 
 
@@ -89,7 +117,7 @@ SMALL_BATCH_LISTS = dict(
         (256, 256, 4, 8, 8), (48, 16, 1, 20, 17)],
   convt=[(32, 16, 2, 24, 16), (64, 32, 3, 8, 8), (256, 128, 4, 8, 8), (128, 64, 2, 5, 7)],
   act=[(16, 2, 16, 24, 'pool'), (64, 3, 8, 8, 'pool'), (256, 2, 4, 4, 'pool')],
-  hand=[(5, 5, 3), (4, 5, 3)], xc_auto=[(3, 16, 128, 32), (4, 16, 64, 16), (2, 5, 128, 32)], xc_update=[])
+  hand=[(5, 5, 3), (4, 5, 3)], xc_auto=[(3, 16, 128, 32), (4, 16, 64, 16), (2, 5, 128, 32)], xc_update=[], xc_exact=False)
 
 
 def ragged_regimes():
@@ -109,7 +137,14 @@ def _show(regimes):
 
 
 def test_the_gpu_suite_reaches_every_regime_of_the_update():
-  need = D.product_regimes(32) | ragged_regimes()
+  need = D.product_regimes(32) | D.rollout_regimes(256) | ragged_regimes()
+  # the mixed operand pairs of the backward under bf16 features and the rollout's one channel group are among them
+  for H, h in ((128, 32), (64, 16)):
+    assert ('xcorr toeplitz', 'd/dx', '%d/%d' % (H, h), 'bf16', 'channels/workgroup>1', 'even channel groups', 'one pass', 'f32 x bf16') in need
+    assert ('xcorr toeplitz', 'd/dw', '%d/%d' % (H, h), 'bf16', 'channels/workgroup>1', 'even channel groups', 'one pass', 'bf16 x f32') in need
+  for prec, pair in (('bf16', 'bf16 x bf16'), ('bf16x3', 'f32 x f32')):
+    assert ('xcorr toeplitz', 'forward', '64/16', prec, 'channels/workgroup>1', 'even channel groups', 'one pass', pair) in need
+    assert ('xcorr rows', prec, pair) in need
   missing = need - regimes_reached()
   assert not missing, 'dispatch regimes of the update that no GPU test reaches:\n' + _show(missing)
   # and by the tests of the single kernels alone: the whole net's test says that a gradient is off, theirs say which kernel's
@@ -132,7 +167,7 @@ def test_the_product_reaches_what_the_small_batches_never_did():
     for geom in ('128/32', '64/16'):
       for prec in ('bf16', 'bf16x3'):
         r = ('xcorr toeplitz', mode, geom, prec, 'channels/workgroup>1', 'even channel groups',
-             'two-pass sum' if mode == 'forward' else 'one pass')
+             'two-pass sum' if mode == 'forward' else 'one pass', 'f32 x f32')
         # the one exception: test_xcorr_row_product_forward runs the forward at 200 samples on the Toeplitz kernel too
         assert (r in missing) != (r[1:4] == ('forward', '128/32', 'bf16x3')), r
 
@@ -150,6 +185,7 @@ def test_the_hand_worked_figures_of_the_update():
   assert D.act_pixb(32 * 128 * 128, 16) == 512 and D.act_pixb(32 * 97 * 97, 16) == 320 and D.act_pixb(6 * 128 * 128, 16) == 256
   assert D.channel_split(64, 16) == (4, 4) and D.channel_split(32, 16) == (2, 8) and D.channel_split(16, 16) == (1, 16)
   assert D.channel_split(200, 16) == (8, 2) and D.channel_split(50, 16) == (3, 6) and D.channel_split(100, 7) == (3, 3)
+  assert D.channel_split(256, 16) == (16, 1) and D.channel_split(3, 1) == (1, 1) and D.channel_split(3, 16) == (1, 16)
 
 
 def _every_case():
@@ -167,7 +203,8 @@ def _every_case():
     wrw.add((1, B, H, W, cin, 4 * cout)); act.add((4 * B * H * W, cout))
   for C, B, H, W, _ in TC.ACT_CASES:
     act.add((B * H * W, C))
-  for B, C, H, h in TL.XCORR_AUTOGRAD_CASES + TL.XCORR_UPDATE_CASES + [(64, 16, 128, 32), (32, 16, 64, 16), (200, 16, 128, 32)]:
+  for B, C, H, h in TL.XCORR_AUTOGRAD_CASES + TL.XCORR_UPDATE_CASES + [(64, 16, 128, 32), (32, 16, 64, 16), (200, 16, 128, 32)] + \
+      [(B, C, H, h) for H, h in TX.GEOMETRIES for B, C in TX.TOEPLITZ_BC + [(TX.LARGE_BATCH, 16)]]:
     xc.add((B, C, H, h))
   return sorted(wrw), sorted(act), sorted(xc)
 

@@ -85,24 +85,38 @@ def xcorr_scratch_bytes(mode, B, C, H, kh):
   return B * csplit * O * O * 4 if (mode == 0 and csplit > 1) else 0
 
 
-def xcorr_rows_chosen(mode, precision, B, C, H, kh, f32=True, force=None):
-  """`use_rows`: the row-product forward (float32 or bf16 operands of one kind — the entry points of qops.py pass no mixed
-  pair) for 128 / 32 at 192 samples and more; `force` is the SRL_XCORR_ROWS setting of the call ('0', '1' or None)."""
-  if mode != 0 or H != 128 or kh != 32 or C < 1 or C > 16 or (precision == 1 and not f32):
+F32, BF16 = 'f32', 'bf16'                # operand dtypes: a launch's pair is (map, kernel)
+
+
+def xcorr_rows_chosen(mode, precision, B, C, H, kh, pair=(F32, F32), force=None):
+  """`use_rows`: the row-product forward (float32 or bf16 operands of one kind) for 128 / 32 at 192 samples and more; `force`
+  is the SRL_XCORR_ROWS setting of the call ('0', '1' or None).  The forward entry points of qops.py pass no mixed pair;
+  `_XCorrMFMA.backward` does, under bf16 features (`backward_pairs`), and a mixed pair never takes this kernel."""
+  if mode != 0 or H != 128 or kh != 32 or C < 1 or C > 16 or pair[0] != pair[1] or (precision == 1 and pair[0] != F32):
     return False
   if force in ('0', '1'):
     return force == '1'
   return B >= 192
 
 
-def xcorr_regime(mode, precision, B, C, H, kh, f32=True, force=None):
-  if xcorr_rows_chosen(mode, precision, B, C, H, kh, f32, force):
-    return ('xcorr rows', 'bf16x3' if precision else 'bf16')
+def xcorr_regime(mode, precision, B, C, H, kh, pair=(F32, F32), force=None):
+  """`launch` instantiates the Toeplitz kernel per operand pair (precision 1 takes float32 operands only), so the pair is
+  part of the regime."""
+  assert precision == 0 or pair == (F32, F32)
+  if xcorr_rows_chosen(mode, precision, B, C, H, kh, pair, force):
+    return ('xcorr rows', 'bf16x3' if precision else 'bf16', '{} x {}'.format(*pair))
   cper, csplit = channel_split(B, C)
   return ('xcorr toeplitz', ('forward', 'd/dx', 'd/dw')[mode], '{}/{}'.format(H, kh), 'bf16x3' if precision else 'bf16',
           'channels/workgroup>1' if cper > 1 else 'channels/workgroup=1',
           'ragged last channel group' if C % cper else 'even channel groups',
-          'two-pass sum' if (mode == 0 and csplit > 1) else 'one pass')
+          'two-pass sum' if (mode == 0 and csplit > 1) else 'one pass', '{} x {}'.format(*pair))
+
+
+def backward_pairs(features):
+  """The (map, kernel) pair of each mode as `_XCorrMFMA` launches it at precision 0 with features of one dtype: the output
+  gradient is float32 whatever the features are, so under bf16 features d/dx takes a float32 padded gradient with bf16
+  flipped kernels and d/dw bf16 maps with a float32 gradient."""
+  return {0: (features, features), 1: (F32, features), 2: (features, F32)}
 
 
 # ------------------------------------------------------------------------------------------------ the network
@@ -154,14 +168,27 @@ def layer_regimes(l, B, n):
 def product_regimes(minibatch=32):
   """What one Double-DQN update of `minibatch` transitions launches: the online net forward on 2 x minibatch samples
   (states and next states in one pass), the target net on minibatch, the backward on the first minibatch; for the Stack-v0
-  shapes (128 / 32) and the 64 x 64 configuration (64 / 16); the cross-correlation in both precisions."""
+  shapes (128 / 32) and the 64 x 64 configuration (64 / 16); the cross-correlation in both precisions — at precision 0 with
+  float32 features and with bf16 features, whose backward launches the mixed operand pairs."""
   out = set()
   for res_l, res_r in ((128, 32), (64, 16)):
     for l in net_layers(res_l, res_r):
       out |= layer_regimes(l, 2 * minibatch, minibatch)
       out.add(tconv_regime(l['taps'], minibatch, l['r'], l['r'], l['cout']))          # the target net
-    for precision in (0, 1):
-      out.add(xcorr_regime(0, precision, 2 * minibatch, 16, res_l, res_r))
+    for precision, features in ((0, F32), (1, F32), (0, BF16)):
+      pairs = backward_pairs(features)
+      out.add(xcorr_regime(0, precision, 2 * minibatch, 16, res_l, res_r, pairs[0]))
       for mode in (0, 1, 2):
-        out.add(xcorr_regime(mode, precision, minibatch, 16, res_l, res_r))
+        out.add(xcorr_regime(mode, precision, minibatch, 16, res_l, res_r, pairs[mode]))
+  return out
+
+
+def rollout_regimes(chunk=256):
+  """The cross-correlation forward of the rollout at a policy chunk of `chunk` samples (256 and more), bf16 features under
+  autocast or float32 features with the split.  128 / 32 takes the row-product kernel; 64 / 16 has none and runs the Toeplitz
+  forward with ONE CHANNEL GROUP: a workgroup loops over all 16 channels and writes the output itself, in one pass."""
+  out = set()
+  for res_l, res_r in ((128, 32), (64, 16)):
+    out |= {xcorr_regime(0, 0, chunk, 16, res_l, res_r, (BF16, BF16)), xcorr_regime(0, 1, chunk, 16, res_l, res_r)}
+  assert channel_split(chunk, 16) == (16, 1)
   return out
