@@ -9,6 +9,7 @@ Multi-GPU (absent in the reference): one process per GPU, env shard + replay sha
 per update — an all-reduce (RCCL over xGMI) of the flat gradient bucket (~2.13 M fp32 = 8.5 MB), averaged.
 All gradients are views of one contiguous buffer, so the collective needs no packing copies.
 """
+import collections
 import math
 
 import torch
@@ -146,39 +147,79 @@ class KerasAdam(object):
     self.m.copy_(d['m']); self.v.copy_(d['v']); self.state.copy_(d['state'])
 
 
-class GraphedEval(object):
-  """`net(inputs)` without grad, replayed from a hipGraph (torch.cuda.CUDAGraph) for a fixed input signature.
-  The target evaluations of the update are ~200 launches of microsecond kernels each; as a graph each is one launch.
-  The net's parameters are read in place, so optimiser steps and target syncs need no re-capture."""
+# stages: run in this order; stream: 'main' (the caller's current stream) or 'update' (the agent's own); graph: replayed from
+# one hipGraph; draws: that graph samples the replay memory, so the sampling generator is registered with it
+Segment = collections.namedtuple('Segment', 'stages stream graph draws')
 
-  def __init__(self, net):
-    self.net = net
-    self.graph = None
-    self.sig = None
 
-  def _capture(self, inputs):
-    self.static_in = tuple(torch.empty_like(t) for t in inputs)
-    for s, t in zip(self.static_in, inputs):
-      s.copy_(t)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side), torch.no_grad():       # warm-up: library solver search, lazy initialisations
-      for _ in range(2):
-        self.net(self.static_in)
-    torch.cuda.current_stream().wait_stream(side)
-    self.graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_MODE), torch.no_grad():
-      self.static_out = self.net(self.static_in)
+def update_plan(prefetch, world, early, graphs):
+  """Where the stages of one minibatch update run: the list of its `Segment`s in execution order.  The stages are grad (the
+  minibatch at the head of the FIFO, or a fresh draw without prefetch; target evaluations, forward, loss, backward), fifo
+  (shift the slots, draw into the tail; only with prefetch), reduce (all-reduce of the gradient bucket; only with more than
+  one rank), apply (average, optimiser step, priorities), always in this order.  `reduce` is a segment of its own and never
+  part of a graph: the collective stays an ordinary stream-ordered call of whatever backend the process group has.  With
+  `early` (needs prefetch >= 1) so is `grad`, on the update stream, where `train_begin` starts it beside the collect step."""
+  early = bool(early) and prefetch >= 1
+  groups = [['grad'], []] if early else [['grad']]
+  if prefetch:
+    groups[-1].append('fifo')
+  if world > 1:
+    groups += [['reduce'], []]
+  groups[-1].append('apply')
+  draw = 'fifo' if prefetch else 'grad'
+  return [Segment(tuple(g), 'update' if early and i == 0 else 'main', bool(graphs) and g != ['reduce'],
+                  bool(graphs) and draw in g) for i, g in enumerate(groups)]
 
-  def __call__(self, inputs):
-    sig = tuple((tuple(t.shape), t.dtype) for t in inputs)
-    if sig != self.sig:
-      self._capture(inputs)
-      self.sig = sig
-    for s, t in zip(self.static_in, inputs):
-      s.copy_(t)
-    self.graph.replay()
-    return self.static_out
+
+def _clone_slot(slot):
+  return tuple(None if t is None else t.clone() for t in slot)
+
+
+def _copy_slot(dst, src):
+  for d, s in zip(dst, src):
+    if d is not None:
+      d.copy_(s)
+
+
+class MinibatchFifo(object):
+  """`dataset.prefetch(prefetch)` (dqn.py:247-252; config.gin:104 sets 3), restated deterministically.  The reference's
+  background thread keeps `prefetch` minibatches sampled AHEAD of the update that consumes them, so a minibatch was drawn —
+  with the priorities, the importance-weight schedule and the transitions of that moment — about `prefetch` updates before
+  it is used.  Here: `length` slots, filled by as many draws before the first update; every update takes a copy of the
+  oldest, and a new one is drawn in its place before the update's own priorities are written (the producer thread refills as
+  soon as a slot is free).  The slots live at fixed addresses (shift copies), so the whole thing replays from a hipGraph."""
+
+  def __init__(self, length, draw, device):
+    self.length, self._draw, self.device, self.slots = int(length), draw, device, None
+
+  def fill(self):
+    if self.slots is None:
+      self.slots = [_clone_slot(self._draw()) for _ in range(self.length)]
+
+  def head(self):
+    return _clone_slot(self.slots[0])
+
+  def advance(self):
+    for dst, src in zip(self.slots, self.slots[1:]):
+      _copy_slot(dst, src)
+    _copy_slot(self.slots[-1], self._draw())
+
+  def state(self):
+    return [_clone_slot(slot) for slot in self.slots]
+
+  def load(self, saved, captured):
+    """After the replay memory was restored.  saved: the `state()` of the saved run, or None; captured: a captured update
+    reads the slots at their addresses, so they stay."""
+    if saved is not None and len(saved) == self.length:
+      if self.slots is None:
+        self.slots = [tuple(None if t is None else torch.empty_like(t, device=self.device) for t in slot) for slot in saved]
+      for dst, src in zip(self.slots, saved):
+        _copy_slot(dst, src)
+    elif self.slots is not None and not captured:
+      self.slots = None                      # minibatches drawn from the memory that was just replaced
+    elif self.slots is not None:
+      for slot in self.slots:
+        _copy_slot(slot, self._draw())
 
 
 class DQN(object):
@@ -282,19 +323,19 @@ class DQN(object):
     self._double = double
     # prefetch: how many minibatches are sampled ahead of the update that uses them (dqn.py:247-252; None / 0 = none)
     self._prefetch = int(prefetch or 0)
-    self._fifo = None
+    self._fifo = MinibatchFifo(self._prefetch, self._draw, self.device) if self._prefetch else None
     self._last_sample_indexes = None
     self._gen = torch.Generator(device=self.device)
     if seed is not None:
       self._gen.manual_seed(int(seed) + 1)
     self._policy_op = policy_op     # optional fused rollout head (stackrl_amd.qops.FusedPolicy)
     self.policy_timer = None        # optional object with start() / stop() called around every policy evaluation (bench.py)
-    # graphs: replay the no-grad target evaluations of the update from hipGraphs (HIP device only)
+    # graphs: the update — prioritised sampling, target evaluation, forward, backward, Adam, priority update: hundreds of
+    # launches of mostly microsecond kernels — replayed from hipGraphs, one per graphed segment of `update_plan` (HIP device
+    # only).  Everything they read or write lives at fixed addresses (replay tensors, trackers, FIFO slots, flat gradient and
+    # parameter buckets, Adam state, schedule scalars) and the nets' parameters are updated in place, so target syncs and
+    # checkpoints need no re-capture.  The first `_GRAPH_WARMUP` updates are eager and serial.
     self._graphs = bool(graphs) and self.device.type == 'cuda'
-    self._g_target = GraphedEval(self._target_q_net) if self._graphs else None
-    self._g_online = GraphedEval(self._q_net) if self._graphs else None
-    self._train_graph = None
-    self._graph_calls = 0
     # early_gradient: `train_begin()` starts the gradient half of the next update — target evaluation, forward, loss,
     # backward, on the minibatch at the head of the prefetch FIFO, which was drawn `prefetch` updates ago and does not depend
     # on the collect step of this iteration — on a stream of its own, beside the collect step; `train()` then completes the
@@ -302,8 +343,13 @@ class DQN(object):
     # the same order per tensor as the serial update: identical results (tests/test_learner_gpu.py).  Needs prefetch >= 1.
     self._early = bool(early_gradient) and self.device.type == 'cuda' and self._prefetch >= 1
     self._upd_stream = torch.cuda.Stream(device=self.device) if self._early else None
-    self._pending = None                    # outputs of a gradient half started by train_begin()
-    self._grad_graph = self._tail_graph = None
+    self._plan = update_plan(self._prefetch, self._world, self._early, self._graphs)
+    self._warmup_plan = update_plan(self._prefetch, self._world, False, False)
+    self._warmup = self._GRAPH_WARMUP if self._graphs else 0
+    self._updates = 0                       # updates run by this object (a restored `iterations` is not that)
+    self._captured = {}                     # index of a graphed segment of `_plan` -> its hipGraph
+    self._running = None                    # the plan of an update whose first segment has run and the others not yet
+    self._out = None                        # what `grad` returned
     # the loss and its gradient as one hand-written kernel (csrc/learner.hip) on a HIP device
     self._fused = self.device.type == 'cuda'
     self._ws = {}
@@ -311,6 +357,7 @@ class DQN(object):
     # kernels of csrc/train_conv.hip instead of the library's (stackrl_amd/qtrain.py; None = on a HIP device whenever the
     # net and the optimiser allow it: the config.gin network over the flat Keras-Adam bucket)
     self._hand = self._hand_t = None
+    self._hand_cover_checked = False
     if hand_convs is None:
       hand_convs = self._fused and isinstance(self._optimizer, KerasAdam) and self._hand_supported()
     if hand_convs:
@@ -456,9 +503,9 @@ class DQN(object):
         rewards = rewards * self._reward_scale
       if self._gamma == 0 and not self._n_step:
         return rewards
-      tq = self._g_target(next_states) if self._graphs else self._target_q_net(next_states)
+      tq = self._target_q_net(next_states)
       if self._double:
-        a = torch.argmax(self._g_online(next_states) if self._graphs else self._q_net(next_states), dim=-1)
+        a = torch.argmax(self._q_net(next_states), dim=-1)
         tq = tq.gather(1, a[:, None])[:, 0]
       else:
         tq = tq.amax(dim=-1)
@@ -489,37 +536,14 @@ class DQN(object):
     return (indexes, weights) + tuple(states) + (actions, rewards) + tuple(next_states) + (terminal,)
 
   def _next_minibatch(self):
-    """`next(self._replay_memory_iter)` (dqn.py:399-405).  The reference reads its minibatches through
-    `dataset.prefetch(prefetch)` (dqn.py:247-252; config.gin:104 sets 3): a background thread keeps `prefetch` minibatches
-    sampled AHEAD of the update that consumes them, so a minibatch was drawn — with the priorities, the importance-weight
-    schedule and the transitions of that moment — about `prefetch` updates before it is used.  Restated deterministically:
-    a FIFO of `prefetch` minibatches, filled on the first call; every update takes the oldest and a new one is drawn in its
-    place before the update's own priorities are written (the producer thread refills as soon as a slot is free).  The slots
-    live at fixed addresses (shift copies), so the whole thing replays from the update's hipGraph."""
-    k = self._prefetch
-    if not k:
-      flat = self._draw()
-    else:
-      flat = self._peek_minibatch()
-      self._advance_fifo()
-    return self._split_minibatch(flat)
-
-  def _peek_minibatch(self):
-    """A copy of the minibatch at the head of the FIFO (filled with `prefetch` draws on the first call)."""
+    """`next(self._replay_memory_iter)` (dqn.py:399-405): the oldest minibatch of the FIFO, which then moves on
+    (`MinibatchFifo`), or a fresh draw without prefetch."""
     if self._fifo is None:
-      self._fifo = [tuple(None if t is None else t.clone() for t in self._draw()) for _ in range(self._prefetch)]
-    return tuple(None if t is None else t.clone() for t in self._fifo[0])
-
-  def _advance_fifo(self):
-    """The head leaves, a new minibatch is drawn into the tail (slots at fixed addresses: shift copies)."""
-    k = self._prefetch
-    for i in range(k - 1):
-      for dst, src in zip(self._fifo[i], self._fifo[i + 1]):
-        if dst is not None:
-          dst.copy_(src)
-    for dst, src in zip(self._fifo[k - 1], self._draw()):
-      if dst is not None:
-        dst.copy_(src)
+      return self._split_minibatch(self._draw())
+    self._fifo.fill()
+    flat = self._fifo.head()
+    self._fifo.advance()
+    return self._split_minibatch(flat)
 
   @staticmethod
   def _split_minibatch(flat):
@@ -529,82 +553,76 @@ class DQN(object):
     next_states, terminal = flat[4 + ns:4 + 2 * ns], flat[4 + 2 * ns]
     return indexes, weights, (states, actions, rewards, next_states, terminal)
 
-  def _forward_backward(self, peek=False):
-    """First half of one minibatch update (dqn.py:397-469): sample, target evaluations, forward, loss, backward into the
-    flat gradient bucket.  Returns (loss, mean TD error, indexes, |TD|, new priorities or None).
-    peek: take the head of the FIFO and leave the FIFO as it is (`train_begin`; `_advance_fifo` follows in `train`)."""
+  # ---- the four stages of an update (`update_plan`)
+  def _grad(self):
+    """Stage `grad` (dqn.py:397-469): the minibatch (a copy of the FIFO's head, which stays; a fresh draw without prefetch),
+    target evaluations, forward, loss, backward into the flat gradient bucket.  Draws no random numbers with prefetch and
+    writes neither the replay memory nor the FIFO.  Returns (loss, mean TD error, indexes, |TD|, new priorities or None)."""
     indexes, weights, (states, actions, rewards, next_states, terminal) = \
-      self._split_minibatch(self._peek_minibatch()) if peek else self._next_minibatch()
+      self._split_minibatch(self._draw() if self._fifo is None else self._fifo.head())
     if not self._bias_compensation:
       weights = None
     self._last_sample_indexes = indexes
-    new_logits = None
-    if self._fused and not (self._gamma == 0 and not self._n_step):
-      # target evaluations, then loss, mean TD, |TD|, new priorities and d loss / d Q(s, .) in one kernel (dqn.py:408-469)
-      from stackrl_amd import qops
-      if self._hand is not None:
-        # hand-written convolutions: Q_target(s', .), then Q(s, .) and Q(s', .) of the online net in ONE pass over the 2 mb
-        # samples (activations saved; the backward runs over the first mb)
-        mb = int(actions.shape[0])
-        self._hand.refresh()
-        with torch.no_grad():
-          tq = self._hand_t.forward(next_states)
-          if self._n_step:
-            rewards = (self._gamma_r * rewards).sum(dim=-1)
-        if self._double:
-          both = tuple(torch.cat([a, b]) for a, b in zip(states, next_states))
-          q2 = self._hand.forward(both, save=True)
-          q_all, qo = q2[:mb], q2[mb:].detach()
-        else:
-          q_all, qo = self._hand.forward(states, save=True), None
-        loss, mtd, td_abs, new_logits, grad_q = qops.td_epilogue(
-          q_all.detach(), qo, tq, actions, rewards, terminal, weights, self._gamma, self._huber_delta, self._reward_scale,
-          self._double, self._replay_memory.epsilon, self._ws)
-        # no zero-fill of the gradient bucket: the hand-written backward writes every element of every parameter's gradient
-        # (tests/test_train_conv_gpu.py starts it from NaN); the alignment padding between parameters keeps its initial zeros
-        first = not getattr(self, '_hand_cover_checked', False) and not torch.cuda.is_current_stream_capturing()
-        if first:
-          # once, on the first eager update: every parameter's gradient starts from NaN, so that a parameter the hand-written
-          # backward does not write (a layer HandNet does not cover, a frozen or non-dueling variant) cannot keep the
-          # previous step's — or, with several ranks, the previously all-reduced — value unnoticed
-          for p in self._q_net.parameters():
-            p.grad.fill_(float('nan'))
-        self._hand.backward(grad_q)
-        if first:
-          self._hand_cover_checked = True
-          missed = [n for n, p in self._q_net.named_parameters() if not bool(torch.isfinite(p.grad).all())]
-          if missed:
-            raise RuntimeError('HandNet.backward left (part of) these gradients unwritten: {}'.format(missed))
-        return loss, mtd, indexes, td_abs, new_logits
-      with torch.no_grad():
-        tq = self._g_target(next_states) if self._graphs else self._target_q_net(next_states)
-        qo = (self._g_online(next_states) if self._graphs else self._q_net(next_states)) if self._double else None
-        if self._n_step:
-          rewards = (self._gamma_r * rewards).sum(dim=-1)
-      q_all = self._q_net(states)
-      loss, mtd, td_abs, new_logits, grad_q = qops.td_epilogue(
-        q_all.detach(), qo, tq, actions, rewards, terminal, weights, self._gamma, self._huber_delta, self._reward_scale,
-        self._double, self._replay_memory.epsilon, self._ws)
-      self._flat_grad.zero_()
-      q_all.backward(grad_q)
-    else:
+    if not self._fused or (self._gamma == 0 and not self._n_step):
       y = self.td_targets(rewards, next_states, terminal)
       q = self._q_net(states).gather(1, actions[:, None])[:, 0]      # one_hot . sum, dqn.py:410-417
       td = q - y
-      mtd = td.mean().detach()
       td_abs = td.abs()
       loss = self.loss_from_td(td_abs, weights)
       self._flat_grad.zero_()
       loss.backward()
-      loss, td_abs = loss.detach(), td_abs.detach()
+      return loss.detach(), td.mean().detach(), indexes, td_abs.detach(), None
+    # target evaluations, then loss, mean TD, |TD|, new priorities and d loss / d Q(s, .) in one kernel (dqn.py:408-469)
+    from stackrl_amd import qops
+    if self._n_step:
+      rewards = (self._gamma_r * rewards).sum(dim=-1)
+    q_all, qo, tq = self._evaluate(states, next_states)
+    loss, mtd, td_abs, new_logits, grad_q = qops.td_epilogue(
+      q_all.detach(), qo, tq, actions, rewards, terminal, weights, self._gamma, self._huber_delta, self._reward_scale,
+      self._double, self._replay_memory.epsilon, self._ws)
+    if self._hand is None:
+      self._flat_grad.zero_()
+      q_all.backward(grad_q)
+    elif self._hand_cover_checked or torch.cuda.is_current_stream_capturing():
+      # no zero-fill of the gradient bucket: the hand-written backward writes every element of every parameter's gradient
+      # (tests/test_train_conv_gpu.py starts it from NaN); the alignment padding between parameters keeps its initial zeros
+      self._hand.backward(grad_q)
+    else:
+      self._hand_backward_checking_cover(grad_q)
     return loss, mtd, indexes, td_abs, new_logits
 
-  def _all_reduce(self):
-    """The one collective of the update: the flat gradient bucket summed over the ranks (RCCL over xGMI)."""
-    dist.all_reduce(self._flat_grad, op=dist.ReduceOp.SUM, group=self._pg)
+  def _evaluate(self, states, next_states):
+    """(Q(s, .) to differentiate, Q(s', .) of the online net without grad or None (not double), Q_target(s', .))."""
+    if self._hand is None:
+      with torch.no_grad():
+        tq = self._target_q_net(next_states)
+        qo = self._q_net(next_states) if self._double else None
+      return self._q_net(states), qo, tq
+    # hand-written convolutions: Q_target(s', .), then Q(s, .) and Q(s', .) of the online net in ONE pass over the 2 mb
+    # samples (activations saved; the backward runs over the first mb)
+    self._hand.refresh()
+    with torch.no_grad():
+      tq = self._hand_t.forward(next_states)
+    if not self._double:
+      return self._hand.forward(states, save=True), None, tq
+    mb = int(states[0].shape[0])
+    q2 = self._hand.forward(tuple(torch.cat([a, b]) for a, b in zip(states, next_states)), save=True)
+    return q2[:mb], q2[mb:].detach(), tq
+
+  def _hand_backward_checking_cover(self, grad_q):
+    """Once, on the first eager update: every parameter's gradient starts from NaN, so that a parameter the hand-written
+    backward does not write (a layer HandNet does not cover, a frozen or non-dueling variant) cannot keep the previous
+    step's — or, with several ranks, the previously all-reduced — value unnoticed."""
+    for p in self._q_net.parameters():
+      p.grad.fill_(float('nan'))
+    self._hand.backward(grad_q)
+    self._hand_cover_checked = True
+    missed = [n for n, p in self._q_net.named_parameters() if not bool(torch.isfinite(p.grad).all())]
+    if missed:
+      raise RuntimeError('HandNet.backward left (part of) these gradients unwritten: {}'.format(missed))
 
   def _apply(self, indexes, td_abs, new_logits):
-    """Second half (dqn.py:470-476): average over the ranks, optimiser step, new replay priorities."""
+    """Stage `apply` (dqn.py:470-476): average over the ranks, optimiser step, new replay priorities."""
     if self._world > 1:
       self._flat_grad.div_(self._world)
     if isinstance(self._optimizer, KerasAdam):
@@ -614,97 +632,96 @@ class DQN(object):
     if self._prioritized:
       self._replay_memory.update_priorities(indexes, td_abs, logits=new_logits)   # dqn.py:475-476
 
-  def _update(self):
-    """One minibatch update (dqn.py:397-476) without the host-side bookkeeping; returns (loss, mean TD error)."""
-    loss, mtd, indexes, td_abs, new_logits = self._forward_backward()
-    if self._world > 1:
-      self._all_reduce()
-    self._apply(indexes, td_abs, new_logits)
-    return loss, mtd
+  def _stage(self, name):
+    if name == 'grad':
+      self._out = self._grad()
+    elif name == 'fifo':
+      self._fifo.advance()
+    elif name == 'reduce':
+      # the one collective of the update: the flat gradient bucket summed over the ranks (RCCL over xGMI)
+      dist.all_reduce(self._flat_grad, op=dist.ReduceOp.SUM, group=self._pg)
+    else:
+      self._apply(*self._out[2:])
 
+  # ---- where the stages run
   _GRAPH_WARMUP = 3   # eager updates before the capture (library solver search, optimiser state, lazy initialisations)
+
+  @property
+  def _train_graph(self):
+    """The first hipGraph of the serial update, once captured."""
+    return None if self._early else self._captured.get(0)
+
+  @property
+  def _grad_graph(self):
+    """The hipGraph of `grad` on the update stream (`early_gradient`), once captured."""
+    return self._captured.get(0) if self._early else None
+
+  def _run_segment(self, plan, i):
+    """Segment i of `plan`: its stages one after the other, or — a graphed segment — their replay from one hipGraph, which
+    is captured on first use: all graphs in the first one's pool, the sampling generator registered with the one that draws,
+    `grad`'s outputs handed on as the captured tensors themselves."""
+    seg = plan[i]
+    if not seg.graph:
+      for name in seg.stages:
+        self._stage(name)
+      return
+    g = self._captured.get(i)
+    if g is None:
+      mem = self._replay_memory
+      mem.tensor_schedules = True            # the graph reads alpha / beta from the scalars `refresh_schedules` writes
+      g = torch.cuda.CUDAGraph()
+      if seg.draws:
+        g.register_generator_state(mem._gen)
+      with torch.cuda.graph(g, pool=self._captured[0].pool() if i else None, capture_error_mode=CAPTURE_MODE,
+                            stream=self._upd_stream if seg.stream == 'update' else None):
+        for name in seg.stages:
+          self._stage(name)
+      self._captured[i] = g
+    g.replay()
+
+  def _start(self):
+    """What stays eager and comes before the stages, then the first segment of the update."""
+    if self._hand_t is not None:
+      self._hand_t.refresh_if_stale()          # outside any graph: the target net changes only through framework ops
+    if self._graphs:
+      self._replay_memory.refresh_schedules()
+    if self._fifo is not None:
+      self._fifo.fill()
+    plan = self._plan if self._updates >= self._warmup else self._warmup_plan
+    if plan[0].stream == 'update':
+      main, upd = torch.cuda.current_stream(self.device), self._upd_stream
+      upd.wait_stream(main)                    # the weights of the previous update, the FIFO as the previous train() left it
+      with torch.cuda.stream(upd):
+        self._run_segment(plan, 0)
+        if not plan[0].graph:
+          for t in self._out:
+            if torch.is_tensor(t):
+              t.record_stream(main)            # allocated on the update stream, consumed by train() on the current one
+    else:
+      self._run_segment(plan, 0)
+    self._running = plan
 
   def train_begin(self):
     """Start the gradient half of the next update beside the collect step (see `early_gradient`).  Call it before
-    `collect` / `Trainer.collect_step`; `train()` completes the update.  Returns whether anything was started."""
-    if not self._early or self._pending is not None or self._fifo is None:
-      return False                           # (the first update fills the FIFO from the replay memory: serial)
-    if self._graphs and self._grad_graph is None and self._graph_calls < self._GRAPH_WARMUP:
-      return False                           # eager warm-up updates run serially
-    if self._hand_t is not None:
-      self._hand_t.refresh_if_stale()
-    main, upd = torch.cuda.current_stream(self.device), self._upd_stream
-    self._replay_memory.refresh_schedules()
-    upd.wait_stream(main)                    # the weights of the previous update, the FIFO as the previous train() left it
-    with torch.cuda.stream(upd):
-      if not self._graphs:
-        out = self._forward_backward(peek=True)
-        for t in out:
-          if torch.is_tensor(t):
-            t.record_stream(main)            # allocated on the update stream, consumed by train() on the current one
-      else:
-        if self._grad_graph is None:
-          self._capture_early()
-        self._grad_graph.replay()
-        out = self._graph_out_early
-    self._pending = out
+    `collect` / `Trainer.collect_step`; `train()` completes the update.  Returns whether anything was started.  (The first
+    update fills the FIFO from the replay memory and the warm-up updates of `graphs` are serial: nothing to start.)"""
+    if not self._early or self._running is not None or self._fifo.slots is None or self._updates < self._warmup:
+      return False
+    self._start()
     return True
 
-  def _capture_early(self):
-    """The early form of the graph-replayed update: one graph for the gradient half (captured and replayed on the update
-    stream), one for the rest (FIFO shift + draw, optimiser step, priorities) on the current stream; with more than one
-    rank the all-reduce sits between them as an ordinary stream-ordered call."""
-    mem = self._replay_memory
-    mem.tensor_schedules = True
-    g_eval, self._graphs = self._graphs, False       # the target evaluations are part of the graph
-    try:
-      g = torch.cuda.CUDAGraph()
-      with torch.cuda.graph(g, stream=self._upd_stream, capture_error_mode=CAPTURE_MODE):
-        self._graph_out_early = self._forward_backward(peek=True)
-      self._grad_graph = g
-    finally:
-      self._graphs = g_eval
-
-  def _finish_early(self):
-    loss, mtd, indexes, td_abs, new_logits = self._pending
-    self._pending = None
-    torch.cuda.current_stream(self.device).wait_stream(self._upd_stream)
-    if not self._graphs:
-      self._advance_fifo()
-      if self._world > 1:
-        self._all_reduce()
-      self._apply(indexes, td_abs, new_logits)
-      return loss, mtd
-    mem = self._replay_memory
-    if self._tail_graph is None:
-      g = torch.cuda.CUDAGraph()
-      g.register_generator_state(mem._gen)
-      with torch.cuda.graph(g, pool=self._grad_graph.pool(), capture_error_mode=CAPTURE_MODE):
-        self._advance_fifo()
-      self._fifo_graph = g
-      g2 = torch.cuda.CUDAGraph()
-      with torch.cuda.graph(g2, pool=self._grad_graph.pool(), capture_error_mode=CAPTURE_MODE):
-        self._apply(indexes, td_abs, new_logits)
-      self._tail_graph = g2
-    self._fifo_graph.replay()
-    if self._world > 1:
-      self._all_reduce()
-    self._tail_graph.replay()
-    return loss.clone(), mtd.clone()
-
   def train(self):
-    if self._pending is not None:
-      loss, mtd = self._finish_early()
-    else:
-      if self._hand_t is not None:
-        self._hand_t.refresh_if_stale()        # eagerly, outside any graph: the target net changes only through framework ops
-      if self._graphs and not (self._early and self._fifo is not None and self._graph_calls >= self._GRAPH_WARMUP):
-        loss, mtd = self._train_graphed()
-      else:
-        if self._graphs:
-          self._replay_memory.refresh_schedules()
-          self._graph_calls += 1
-        loss, mtd = self._update()
+    if self._running is None:
+      self._start()
+    plan, self._running = self._running, None
+    if plan[0].stream == 'update':
+      torch.cuda.current_stream(self.device).wait_stream(self._upd_stream)
+    for i in range(1, len(plan)):
+      self._run_segment(plan, i)
+    loss, mtd = self._out[:2]
+    if plan[0].graph:
+      loss, mtd = loss.clone(), mtd.clone()    # the graph's own tensors: the next replay overwrites them
+    self._updates += 1
     self._iterations += 1
     # consumers that cache re-packed weights (qops.FastFeatures) key on this: a graph replay changes the parameters
     # without bumping any tensor version
@@ -718,50 +735,6 @@ class DQN(object):
   def _target_sync_source(self):
     return self._q_net.state_dict()
 
-  def _train_graphed(self):
-    """The whole update — prioritised sampling, target evaluation, forward, backward, Adam, priority update: hundreds of
-    launches of mostly microsecond kernels — replayed as one hipGraph.  Everything it reads or writes lives at fixed
-    addresses (replay tensors, trackers, flat gradient and parameter buckets, Adam state, schedule scalars), the sampling
-    generator is registered with the graph, and the nets' parameters are updated in place, so target syncs and
-    checkpoints need no re-capture.  With more than one rank the update is two graphs around the eager all-reduce of the
-    gradient bucket (sample .. backward | all-reduce | average, Adam, priorities): the collective stays an ordinary
-    stream-ordered call of whatever backend the process group has, and the launch-bound halves are still one launch each."""
-    mem = self._replay_memory
-    mem.refresh_schedules()
-    if self._train_graph is None:
-      self._graph_calls += 1
-      if self._graph_calls <= self._GRAPH_WARMUP:
-        return self._update()
-      mem.tensor_schedules = True
-      g = torch.cuda.CUDAGraph()
-      g.register_generator_state(mem._gen)
-      g_eval = self._graphs
-      self._graphs = False                 # the target evaluations are part of this graph, not graphs of their own
-      try:
-        if self._world == 1:
-          with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-            self._graph_out = self._update()
-        else:
-          with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-            loss, mtd, indexes, td_abs, new_logits = self._forward_backward()
-          self._graph_out = (loss, mtd)
-          g2 = torch.cuda.CUDAGraph()
-          with torch.cuda.graph(g2, pool=g.pool(), capture_error_mode=CAPTURE_MODE):
-            self._apply(indexes, td_abs, new_logits)
-          self._apply_graph = g2
-      finally:
-        self._graphs = g_eval
-      self._train_graph = g
-    return self._replay_update()
-
-  def _replay_update(self):
-    self._train_graph.replay()
-    if self._world > 1:
-      self._all_reduce()
-      self._apply_graph.replay()
-    loss, mtd = self._graph_out
-    return loss.clone(), mtd.clone()
-
   def save_weights(self, path):
     torch.save(self._q_net.state_dict(), path)
 
@@ -774,8 +747,8 @@ class DQN(object):
       d['replay_memory'] = self._replay_memory.state_dict()
       # the minibatches already drawn and waiting (`dataset.prefetch`, dqn.py:247-252): part of the state, or a resumed run
       # would train on freshly drawn ones where the uninterrupted run trains on these
-      if self._fifo is not None:
-        d['prefetched'] = [tuple(None if t is None else t.clone() for t in slot) for slot in self._fifo]
+      if self._fifo is not None and self._fifo.slots is not None:
+        d['prefetched'] = self._fifo.state()
     return d
 
   def load_state_dict(self, d):
@@ -789,33 +762,17 @@ class DQN(object):
       self._q_net._weights_epoch = getattr(self._q_net, '_weights_epoch', 0) + 1   # restored weights: a new epoch, never an earlier one's
       if self._hand_t is not None:
         self._hand_t.refresh()
-    if self._pending is not None:
+    if self._running is not None:
       # a gradient half computed from the weights / minibatch being replaced is in flight on the update stream: wait for
       # it and drop it (the next train() starts over from the restored state)
       torch.cuda.current_stream(self.device).wait_stream(self._upd_stream)
-      self._pending = None
+      self._running = None
     if 'gen' in d:
       self._gen.set_state(d['gen'].cpu())
     if 'replay_memory' in d:
       self._replay_memory.load_state_dict(d['replay_memory'])
-      saved = d.get('prefetched')
-      graphed = self._train_graph is not None or self._grad_graph is not None
-      if saved is not None and len(saved) == self._prefetch:
-        # the waiting minibatches of the saved run, into the slots a captured update reads at their addresses (or new ones)
-        if self._fifo is None:
-          self._fifo = [tuple(None if t is None else t.clone().to(self.device) for t in slot) for slot in saved]
-        else:
-          for slot, src in zip(self._fifo, saved):
-            for dst, t in zip(slot, src):
-              if dst is not None:
-                dst.copy_(t)
-      elif self._fifo is not None and not graphed:
-        self._fifo = None                      # minibatches drawn from the memory that was just replaced
-      elif self._fifo is not None:             # (a captured update reads the slots at their addresses: refill in place)
-        for slot in self._fifo:
-          for dst, src in zip(slot, self._draw()):
-            if dst is not None:
-              dst.copy_(src)
+      if self._fifo is not None:
+        self._fifo.load(d.get('prefetched'), captured=bool(self._captured))
 
   def reseed(self, seed):
     """New streams for exploration and minibatch sampling (a rank that resumes without state of its own)."""

@@ -620,7 +620,7 @@ class FastFeatures(object):
 
   def _refresh(self):
     # `_weights_epoch` is bumped by whoever updates the parameters outside ATen's sight: a hipGraph replay of the
-    # optimiser step (DQN._train_graphed) changes the weights without touching any tensor's version counter
+    # optimiser step (DQN._run_segment) changes the weights without touching any tensor's version counter
     key = tuple(p._version for p in self.net.parameters()) + (id(self.net), getattr(self.net, '_weights_epoch', 0))
     if key == self._key:
       return

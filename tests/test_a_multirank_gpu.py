@@ -11,9 +11,11 @@ torch = pytest.importorskip('torch')
 pytestmark = pytest.mark.gpu
 
 
-def _two_rank_update(rank, world, port, out):
+def _two_rank_update(rank, world, port, out, early=False):
   """One rank of the two-rank rehearsal on ONE GPU (both ranks on device 0, gloo): different net seeds and different
-  replay contents per rank; the update runs eagerly first, then from the two hipGraphs around the all-reduce."""
+  replay contents per rank; the update runs eagerly first, then from the two hipGraphs around the all-reduce.  early: with
+  `early_gradient=True, prefetch=2` and `train_begin()` before every `train()` — the gradient half as a graph of its own on
+  the update stream, then graph / all-reduce / graph."""
   import os
   import torch.distributed as dist
   from stackrl_amd import nets
@@ -25,7 +27,8 @@ def _two_rank_update(rank, world, port, out):
   B = 4
   agent = DQN(net, learning_rate=1e-3, adam_betas=(0.95, 0.95), minibatch_size=4, replay_memory_size=B * 8,
               discount_factor=0.9, collect_batch_size=B, exploration=0.5, prioritization=0.6,
-              priority_bias_compensation=0.5, double=True, seed=100 + rank, xcorr='bf16x3', graphs=True)
+              priority_bias_compensation=0.5, double=True, seed=100 + rank, xcorr='bf16x3', graphs=True,
+              **(dict(early_gradient=True, prefetch=2) if early else {}))
   g = torch.Generator(device='cuda').manual_seed(50 + rank)
   for t in range(7):
     st = (torch.randint(0, 256, (B, 128, 128, 2), generator=g, device='cuda', dtype=torch.uint8),
@@ -33,15 +36,24 @@ def _two_rank_update(rank, world, port, out):
     agent.observe(st, torch.randn(B, generator=g, device='cuda'), torch.zeros(B, dtype=torch.bool, device='cuda'),
                   torch.randint(0, net.n_actions, (B,), generator=g, device='cuda'))
   w0 = torch.cat([p.detach().flatten() for p in agent._params]).clone()
-  losses = [float(agent.train()[0]) for _ in range(DQN._GRAPH_WARMUP + 3)]
+  losses = []
+  for _ in range(DQN._GRAPH_WARMUP + 3):
+    if early:
+      agent.train_begin()
+    losses.append(float(agent.train()[0]))
+  # the derived plan, and every graph of it captured
+  plan = [(s.stages, s.stream, s.graph) for s in agent._plan]
+  want = ([(('grad',), 'update', True), (('fifo',), 'main', True)] if early else [(('grad',), 'main', True)]) + \
+    [(('reduce',), 'main', False), (('apply',), 'main', True)]
+  graphed = plan == want and (agent._grad_graph if early else agent._train_graph) is not None and \
+    sorted(agent._captured) == [i for i, s in enumerate(agent._plan) if s.graph]
   flat = torch.cat([p.detach().flatten() for p in agent._params]).cpu()
   gathered = [torch.zeros_like(flat) for _ in range(world)]
   dist.all_gather(gathered, flat)
   lo = torch.tensor(losses); lall = [torch.zeros_like(lo) for _ in range(world)]
   dist.all_gather(lall, lo)
   if rank == 0:
-    torch.save({'replicas_equal': bool(torch.equal(gathered[0], gathered[1])), 'graphed': agent._train_graph is not None
-                and getattr(agent, '_apply_graph', None) is not None, 'moved': bool(not torch.equal(flat, w0.cpu())),
+    torch.save({'replicas_equal': bool(torch.equal(gathered[0], gathered[1])), 'graphed': graphed, 'moved': bool(not torch.equal(flat, w0.cpu())),
                 'losses_differ': bool(not torch.equal(lall[0], lall[1])), 'finite': bool(torch.isfinite(lo).all())}, out)
   dist.destroy_process_group()
 
@@ -49,15 +61,18 @@ def _two_rank_update(rank, world, port, out):
 def test_two_rank_graphed_update_keeps_replicas_equal(tmp_path):
   """Multi-GPU update path on one GPU: two processes (gloo, both on device 0), nets built from different seeds, different
   replay shards; after eager and hipGraph-replayed updates (two graphs around the all-reduce of the gradient bucket) the
-  replicas hold bit-identical weights while their local losses differ."""
+  replicas hold bit-identical weights while their local losses differ.  Then the same with the early gradient half (a third
+  graph, on the update stream)."""
   import os
   import torch.multiprocessing as mp
   if torch.cuda.is_initialized():
     pytest.skip('this process has already initialised the GPU: its children must not be forked from it')
-  out = str(tmp_path / 'res.pt')
-  mp.start_processes(_two_rank_update, args=(2, 29000 + os.getpid() % 2000, out), nprocs=2, join=True, start_method='fork')
-  res = torch.load(out)
-  assert res == {'replicas_equal': True, 'graphed': True, 'moved': True, 'losses_differ': True, 'finite': True}
+  for early in (False, True):
+    out = str(tmp_path / 'res{}.pt'.format(int(early)))
+    mp.start_processes(_two_rank_update, args=(2, 29000 + os.getpid() % 2000 + 2000 * early, out, early), nprocs=2, join=True,
+                       start_method='fork')
+    res = torch.load(out)
+    assert res == {'replicas_equal': True, 'graphed': True, 'moved': True, 'losses_differ': True, 'finite': True}, early
 
 
 def _run_bench(extra_env, *flags):

@@ -519,6 +519,36 @@ def test_resume_continues_the_uninterrupted_run_with_prefetched_minibatches():
     assert torch.equal(p, q)
 
 
+def test_update_plan_against_the_table_of_modes():
+  """`dqn.update_plan`: which stages of an update run together, on which stream, whether as a hipGraph, and which graph has
+  the sampling generator registered — against the table written out by hand.  The stage order is always grad, fifo, reduce,
+  apply; a segment ends at `reduce`, which is never inside a graph; with `early` (needs prefetch) `grad` ends its segment
+  too, on the update stream; the draw is in `grad` without prefetch and in `fifo` with it.  Without graphs: the same stages
+  in the same segments, none a graph, no generator registered."""
+  from stackrl_amd.dqn import update_plan
+  M, U = 'main', 'update'
+  table = {  # (prefetch, world, early): [(stages, stream, graph, draws)]
+    (0, 1, False): [(('grad', 'apply'), M, True, True)],
+    (0, 1, True): [(('grad', 'apply'), M, True, True)],
+    (0, 2, False): [(('grad',), M, True, True), (('reduce',), M, False, False), (('apply',), M, True, False)],
+    (0, 2, True): [(('grad',), M, True, True), (('reduce',), M, False, False), (('apply',), M, True, False)],
+    (2, 1, False): [(('grad', 'fifo', 'apply'), M, True, True)],
+    (2, 1, True): [(('grad',), U, True, False), (('fifo', 'apply'), M, True, True)],
+    (2, 2, False): [(('grad', 'fifo'), M, True, True), (('reduce',), M, False, False), (('apply',), M, True, False)],
+    (2, 2, True): [(('grad',), U, True, False), (('fifo',), M, True, True), (('reduce',), M, False, False), (('apply',), M, True, False)],
+  }
+  for (prefetch, world, early), want in table.items():
+    plan = update_plan(prefetch, world, early, True)
+    assert [tuple(s) for s in plan] == want, (prefetch, world, early)
+    stages = [name for s in plan for name in s.stages]
+    assert stages == [n for n in ('grad', 'fifo', 'reduce', 'apply') if (n != 'fifo' or prefetch) and (n != 'reduce' or world > 1)]
+    assert all(s.stages == ('reduce',) and not s.graph for s in plan if 'reduce' in s.stages)
+    assert sum(s.draws for s in plan) == 1
+    eager = update_plan(prefetch, world, early, False)
+    assert [(s.stages, s.stream) for s in eager] == [(s.stages, s.stream) for s in plan]
+    assert not any(s.graph or s.draws for s in eager)
+
+
 def _ckpt_rank(rank, world, port, d, out):
   import torch.distributed as dist
   from stackrl_amd.training import Trainer

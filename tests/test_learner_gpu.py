@@ -297,8 +297,9 @@ def test_end_to_end_dqn_iterations(ref_pool):
 
 def test_update_with_mfma_xcorr_and_graphs_tracks_library_update(ref_pool):
   """The same seeded DQN run with (a) the library formulation of the cross-correlation, eager, and (b) the MFMA
-  bf16x3 kernels with the target evaluations replayed from hipGraphs: identical replay contents and sampled
-  minibatches (same RNG), losses within the fp32-class tolerance of the split, weights staying close."""
+  bf16x3 kernels with `graphs=True` (three eager warm-up updates, then the whole update replayed from a hipGraph):
+  identical replay contents and sampled minibatches (same RNG), losses within the fp32-class tolerance of the split,
+  weights staying close."""
   from stackrl_amd import env as envs, nets, qops
   from stackrl_amd.dqn import DQN, PolynomialDecay
   from stackrl_amd.training import Trainer
@@ -975,20 +976,23 @@ def test_convt2x2_gemm_matches_torch_fp64(cin, cout, H, W, f32):
 def test_prefetch_fifo_replays_from_the_update_graph(ref_pool):
   """`DQN(prefetch=2)` (the reference's `dataset.prefetch`, dqn.py:247-252): the FIFO of minibatches lives at fixed
   addresses, so the hipGraph-replayed update must use, update for update, the same minibatches as the eager one and land on
-  the same weights (the update's kernels are deterministic); and the hand-written update (`HandNet`) against the module
+  the same weights (the update's kernels are deterministic), and so must the one without prefetch, whose minibatch is drawn
+  inside the graph; and the hand-written update (`HandNet`) against the module
   graph through the library within the float32-class tolerance of the cross-correlation."""
   from stackrl_amd import env as envs, nets, qops
   from stackrl_amd.dqn import DQN, PolynomialDecay
   from stackrl_amd.training import Trainer
   B, L = 8, 4
   runs = []
-  for kw in (dict(graphs=False), dict(graphs=True), dict(graphs=False, hand_convs=False)):
+  for kw in (dict(graphs=False), dict(graphs=True), dict(graphs=False, hand_convs=False),
+             dict(graphs=False, prefetch=0), dict(graphs=True, prefetch=0)):
+    kw.setdefault('prefetch', 2)
     env = envs.make('Stack-v0', n_parallel=B, seed=5, pool=ref_pool, episode_length=L)
     net = nets.DeepQSiamFCN(env.observation_spec, seed=2).cuda()
     agent = DQN(net, learning_rate=6.25e-5, adam_betas=(0.95, 0.95), minibatch_size=8, replay_memory_size=B * 16,
                 discount_factor=.966667, collect_batch_size=B, exploration=1.0, prioritization=0.6,
                 priority_bias_compensation=PolynomialDecay(0.4, 400000, 1.0), double=True, seed=9,
-                policy_op=qops.FusedPolicy(), xcorr='bf16x3', prefetch=2, **kw)
+                policy_op=qops.FusedPolicy(), xcorr='bf16x3', **kw)
     assert (agent._hand is not None) == kw.get('hand_convs', True)
     tr = Trainer(env, agent)
     tr.initialize(num_steps=10)
@@ -998,14 +1002,16 @@ def test_prefetch_fifo_replays_from_the_update_graph(ref_pool):
       used.append(agent._last_sample_indexes.clone()); losses.append(float(loss))
     runs.append((used, losses, [p.detach().clone() for p in net.parameters()], agent._train_graph is not None))
     env.close()
-  (ua, la, wa, ga), (ub, lb, wb, gb), (uc, lc, wc, gc) = runs
-  assert not ga and gb and not gc
-  # the graph's own `indexes` tensor is static: what it held after each replay is what that update used
-  for x, y in zip(ua, ub):
-    assert torch.equal(x, y)
-  assert la == lb
-  for p, q in zip(wa, wb):
-    assert torch.equal(p, q)
+  (ua, la, wa, ga), (ub, lb, wb, gb), (uc, lc, wc, gc), (ud, ld, wd, gd), (ue, le, we, ge) = runs
+  assert not ga and gb and not gc and not gd and ge
+  # the graph's own `indexes` tensor is static: what it held after each replay is what that update used.  Without prefetch
+  # (ud, ue) the draw is part of the gradient half, and its generator registered with that graph
+  for (ux, lx, wx), (uy, ly, wy) in (((ua, la, wa), (ub, lb, wb)), ((ud, ld, wd), (ue, le, we))):
+    for x, y in zip(ux, uy):
+      assert torch.equal(x, y)
+    assert lx == ly
+    for p, q in zip(wx, wy):
+      assert torch.equal(p, q)
   for x, y in zip(ua[:1], uc[:1]):         # the library path draws the same first minibatch; later priorities differ in the last bits
     assert torch.equal(x, y)
   assert abs(la[0] - lc[0]) <= 1e-3 * max(1e-6, abs(lc[0]))
@@ -1051,13 +1057,14 @@ def test_early_gradient_equals_the_serial_update(ref_pool, graphs):
   """`DQN(early_gradient=True)`: the gradient half of an update (target evaluation, forward, loss, backward on the minibatch
   at the head of the prefetch FIFO) runs on its own stream beside the collect step, the rest (new minibatch into the FIFO,
   optimiser step, priorities) after it.  Same operands, same operations: losses, sampled indexes, priorities and weights are
-  those of the serial update, bit for bit — eager and replayed from hipGraphs, through a target sync."""
+  those of the serial update, bit for bit — eager and replayed from hipGraphs, through a target sync; and so are those of a
+  loop that calls `train_begin()` only on every other iteration (`train()` then runs the gradient half itself)."""
   from stackrl_amd import env as envs, nets, qops
   from stackrl_amd.dqn import DQN, PolynomialDecay
   from stackrl_amd.training import Trainer
   B, L = 64, 3
   runs = []
-  for early in (False, True):
+  for early, skip in ((False, False), (True, False), (True, True)):
     env = envs.make('Stack-v0', n_parallel=B, seed=5, pool=ref_pool, episode_length=L, side_stream=True)
     net = nets.DeepQSiamFCN(env.observation_spec, seed=2).cuda()
     agent = DQN(net, learning_rate=6.25e-5, adam_betas=(0.95, 0.95), minibatch_size=8, replay_memory_size=B * 8,
@@ -1065,21 +1072,85 @@ def test_early_gradient_equals_the_serial_update(ref_pool, graphs):
                 priority_bias_compensation=PolynomialDecay(0.4, 400000, 1.0), double=True, seed=9,
                 policy_op=qops.FusedPolicy(fast=True), xcorr='bf16x3', prefetch=2, graphs=graphs, early_gradient=early)
     assert agent._early == early
+    if skip:                               # a loop that starts the gradient half early only on every other iteration
+      begin, calls = agent.train_begin, []
+      def every_other():
+        calls.append(len(calls) % 2 == 0 and begin())
+        return calls[-1]
+      agent.train_begin = every_other
     tr = Trainer(env, agent)
     tr.initialize(num_steps=2)
     losses = tr.run(11)
+    if skip:                               # some updates were started early; those of the odd iterations were not
+      assert len(calls) == 11 and any(calls)
     started = agent._grad_graph is not None if graphs else None
     mem = agent._replay_memory
     runs.append((losses.clone(), [p.detach().clone() for p in net.parameters()], [p.detach().clone() for p in agent._target_q_net.parameters()],
                  mem._logits.clone(), mem._actions.clone(), agent._last_sample_indexes.clone(), started))
     env.close()
-  a, b = runs
-  assert b[6] in (None, True), 'the early form of the graph was never captured'
-  assert torch.equal(a[4], b[4]), 'actions'
-  assert torch.equal(a[0], b[0]), 'losses {} vs {}'.format(a[0].tolist(), b[0].tolist())
-  assert torch.equal(a[5], b[5]) and torch.equal(a[3], b[3]), 'sampled indexes / priorities'
-  for p, q in zip(a[1] + a[2], b[1] + b[2]):
-    assert torch.equal(p, q)
+  a = runs[0]
+  for b in runs[1:]:
+    assert b[6] in (None, True), 'the early form of the graph was never captured'
+    assert torch.equal(a[4], b[4]), 'actions'
+    assert torch.equal(a[0], b[0]), 'losses {} vs {}'.format(a[0].tolist(), b[0].tolist())
+    assert torch.equal(a[5], b[5]) and torch.equal(a[3], b[3]), 'sampled indexes / priorities'
+    for p, q in zip(a[1] + a[2], b[1] + b[2]):
+      assert torch.equal(p, q)
+
+
+@pytest.mark.parametrize('graphs,early', [(True, False), (True, True), (False, True)])
+def test_resume_under_captured_graphs_continues_the_uninterrupted_run(graphs, early):
+  """`state_dict` / `load_state_dict` of an agent whose update is replayed from hipGraphs and / or started early, with
+  prefetched minibatches waiting: (a) a fresh agent with other seeds that loads the state, (b) the same agent loading it back —
+  its FIFO slots and captured graphs stay, the state goes into them in place — and (c) the same agent loading it while a
+  gradient half started by `train_begin()` is in flight, which is dropped, all reproduce the uninterrupted run's next four
+  updates bit for bit: losses, weights and priorities."""
+  import copy
+  from stackrl_amd import nets
+  from stackrl_amd.dqn import DQN
+  B = 4
+
+  def make(seed):
+    agent = DQN(nets.DeepQSiamFCN(seed=seed).cuda(), learning_rate=1e-3, adam_betas=(0.95, 0.95), minibatch_size=4,
+                replay_memory_size=B * 8, discount_factor=0.9, collect_batch_size=B, exploration=0.5, prioritization=0.6,
+                priority_bias_compensation=0.5, double=True, seed=seed, xcorr='bf16x3', target_update_period=3, prefetch=2,
+                graphs=graphs, early_gradient=early)
+    g = torch.Generator(device='cuda').manual_seed(50 + seed)
+    for t in range(8):
+      st = (torch.randint(0, 256, (B, 128, 128, 2), generator=g, device='cuda', dtype=torch.uint8),
+            torch.randint(0, 256, (B, 32, 32, 1), generator=g, device='cuda', dtype=torch.uint8))
+      agent.observe(st, torch.randn(B, generator=g, device='cuda'), torch.zeros(B, dtype=torch.bool, device='cuda'),
+                    torch.randint(0, agent._n_actions, (B,), generator=g, device='cuda'))
+    return agent
+
+  def update(agent):
+    agent.train_begin()
+    return float(agent.train()[0])
+
+  def four(agent):
+    return ([update(agent) for _ in range(4)], [p.detach().clone() for p in agent._params], agent._replay_memory._logits.clone())
+
+  def same(x, y):
+    return x[0] == y[0] and all(torch.equal(p, q) for p, q in zip(x[1], y[1])) and torch.equal(x[2], y[2])
+
+  a = make(3)
+  for _ in range(DQN._GRAPH_WARMUP + 2):
+    update(a)
+  assert (a._train_graph is not None, a._grad_graph is not None) == (graphs and not early, graphs and early)
+  d = copy.deepcopy(a.state_dict())     # (the nets' state dicts are views of the live parameters)
+  assert len(d['prefetched']) == 2
+  want = four(a)
+  b = make(99)
+  b.load_state_dict(d)
+  assert same(four(b), want), '(a) a fresh agent'
+  a.load_state_dict(d)
+  got = four(a)
+  print('(b) losses', got[0], 'want', want[0])
+  assert same(got, want), '(b) the same agent, slots and graphs in place'
+  if early:
+    assert a.train_begin()
+    a.load_state_dict(d)
+    assert same(four(a), want), '(c) a gradient half in flight is dropped'
 
 
 @pytest.mark.parametrize('n', [5, 1024, 65536, 300001])

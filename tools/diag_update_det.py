@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Is the DQN update's gradient (hand-written convolutions, csrc/train_conv.hip) the same while env kernels run on another
-stream?  One fixed minibatch, `DQN._forward_backward` repeated alone and under a stepping env; the flat gradient bucket and
+stream?  One fixed minibatch, `DQN._grad` repeated alone and under a stepping env; the flat gradient bucket and
 the loss compared bit for bit with the first.  SRL_DIAG_QLIB selects the build of libstackrl_qnet.so."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,14 +21,12 @@ agent = DQN(net, learning_rate=6.25e-5, adam_betas=(0.95, 0.95), minibatch_size=
             policy_op=qops.FusedPolicy(fast=True), xcorr='bf16x3', graphs=False, prefetch=0)
 tr = Trainer(env, agent)
 tr.initialize(num_steps=12)
-fixed = agent._next_minibatch()
-fixed = (fixed[0].clone() if fixed[0] is not None else None, fixed[1].clone() if fixed[1] is not None else None,
-         tuple(tuple(t.clone() for t in x) if isinstance(x, (tuple, list)) else x.clone() for x in fixed[2]))
-agent._next_minibatch = lambda: fixed
+fixed = tuple(None if t is None else t.clone() for t in agent._draw())
+agent._draw = lambda: fixed                 # prefetch=0: the `grad` stage draws its minibatch itself
 load_env = envs.VecStackEnv(n_parallel=2048, seed=5, pool=pool, episode_length=8, side_stream=True)
 load_env.reset()()
 def run():
-  loss = agent._forward_backward()[0]
+  loss = agent._grad()[0]
   return agent._flat_grad.clone(), loss.clone()
 g0, l0 = run(); torch.cuda.synchronize()
 print('hand-written update path:', agent._hand is not None)
