@@ -476,6 +476,7 @@ __device__ __forceinline__ Row make_row(v3 d, v3 ra, v3 rb, float ima, const m3&
 // compiler's own pairing of row_solve — (va.c, vb.c), (wa.c, wb.c) across the two bodies — cost 23 moves and two sign flips per
 // turn of 89 vector instructions.)  The operations and their order are row_solve's: fma(-ab.c, dl, wb.c) = fma(ab.c, -dl, wb.c)
 // exactly (the product's sign is exact), the halves of a packed FMA round once each: bit-identical.
+// (srl_k_step no longer runs these: it solves a pair contact on two lanes, HRow / pair_phase below; the other three variants do.)
 struct PRow { f2 ka[3], kb[3], ua[3], ub[3]; float rk, k; };
 struct Vel2 { f2 a[3], b[3]; };   // [c] = (v.c, w.c) of body A / B
 
@@ -817,7 +818,9 @@ __device__ __forceinline__ Point make_pair_point(const Lds& L, int sl, int i) {
   return p;
 }
 
-// one turn of a point: read the velocities of its bodies, three rows, write them back
+// one turn of a point: read the velocities of its bodies, three rows, write them back (the variants without PAIR_SPLIT: one lane
+// in four of a slot's quad works in a turn and runs both bodies' halves of a row one after the other — 67 vector instructions,
+// four LDS reads and four writes; they are throughput-bound and have no registers for a second set of rows)
 template <bool WARM>
 __device__ __forceinline__ void point_turn(const Lds& L, Point& p, float& res) {
   const float ws = L.P->c.warmstart;
@@ -845,6 +848,180 @@ __device__ __forceinline__ void point_turn(const Lds& L, Point& p, float& res) {
   *(float4*)pb = make_float4(u.b[0].x, u.b[0].y, u.b[1].x, u.b[1].y); *(float2*)(pb + 4) = make_float2(u.b[2].x, u.b[2].y);
 }
 
+// ---- the pair turn on TWO lanes, one per body (Variant::PAIR_SPLIT).  In point_turn one lane in four of a slot's quad works and
+// runs the rows of body A and of body B one after the other: the two halves of a row are the same instruction sequence on
+// different constants and meet in one sum.  Here the even lane of a lane pair holds body A's half of a row — k[c] = (d.c, ca.c),
+// u[c] = (d.c ima, aa.c) — and the odd lane body B's with kb NEGATED — k[c] = (-d.c, -cb.c), u[c] = (d.c (-imb), -ab.c).
+// Negation passes exactly through a product and an FMA chain, so the odd lane's s.x + s.y is exactly -(sb.x + sb.y) of
+// prow_solve, and own + partner (one v_add_f32_dpp quad_perm:[1,0,3,2]; IEEE add commutes) is prow_solve's
+// ra - (sb.x + sb.y) on both lanes.  dl, the med3, the accumulated impulse, lim and res are computed on both lanes, bit-equal;
+// each lane applies its own body's three packed FMAs.  The effective mass (ima + ...) + (imb + ...) is formed from the two
+// lanes' parts with the same add: make_row<true>'s tree.  Lanes (0, 1) of the quad take points 0 and 1 of the manifold, lanes
+// (2, 3) points 2 and 3 — two register sets per lane, the turns unrolled — so a body's velocities stay in the lane's registers
+// from a pair's first turn to its second: one LDS hand-off in two is gone, and no register moves.  Both lanes of a pair are in
+// EXEC for every turn: membership comes from the slot's point count and colour, which the quad shares.
+// A turn is 45 vector instructions with one LDS read and write per pair of turns (point_turn: 67, four reads and four writes
+// per turn): +10.6 % at the headline shape for the split alone, +14.5 % with the velocities kept (profiles/pair_split_experiment.md).
+struct HRow { f2 k[3], u[3]; float rk, kk; };   // one body's half of a row; kk = effective mass denominator, rk = 1 / kk
+struct HSet { HRow n, t1, t2; float trk, in, i1, i2; };   // trk = target rk of the normal row (a friction row's target is 0)
+struct PSplit {
+  HSet s0, s1;     // the lane pair's first and second point: points 2 h and 2 h + 1 of the manifold, h = (lane >> 1) & 1
+  float* pvw;      // the lane's own body's velocities in LDS (Lds::VW)
+  int np;          // contact points of the lane's slot (0: none)
+  int colour;
+  float mu;
+};
+
+__device__ __forceinline__ float quad_partner(float x) {   // the value of lane ^ 1
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true));
+}
+
+// side 0: body A's half, side 1: body B's.  Called by both lanes of a pair together (the effective mass needs the partner's part).
+__device__ __forceinline__ HRow make_hrow(v3 d, v3 r, float im, const m3& I, bool side) {
+  HRow h;
+  const v3 c = cross(r, d);
+  const v3 a = mmul(I, c);
+  const float part = im + dot(cross(a, r), d);
+  const float k = part + quad_partner(part);
+  const v3 dm = d * (side ? -im : im);
+  h.k[0] = side ? F2(-d.x, -c.x) : F2(d.x, c.x); h.k[1] = side ? F2(-d.y, -c.y) : F2(d.y, c.y); h.k[2] = side ? F2(-d.z, -c.z) : F2(d.z, c.z);
+  h.u[0] = F2(dm.x, side ? -a.x : a.x); h.u[1] = F2(dm.y, side ? -a.y : a.y); h.u[2] = F2(dm.z, side ? -a.z : a.z);
+  h.rk = 1.0f / k; h.kk = k;
+  return h;
+}
+
+__device__ __forceinline__ HSet make_hset(const Lds& L, const float* mp, int i, int np, int body, bool side) {
+  const DevParams& P = *L.P;
+  HSet s;
+  s.trk = 0.0f; s.in = 0.0f; s.i1 = 0.0f; s.i2 = 0.0f;
+  if (i >= np) {   // (uniform over the lane pair)
+    HRow z;
+    z.k[0] = z.k[1] = z.k[2] = z.u[0] = z.u[1] = z.u[2] = F2(0.0f, 0.0f); z.rk = 0.0f; z.kk = 0.0f;
+    s.n = z; s.t1 = z; s.t2 = z;
+    return s;
+  }
+  const float im = L.BC(body)[0];
+  const float* q = mp + 4 + SRL_MP_WORDS * i;
+  const v3 r = mmul(ldm(L.R(body)), ld3(q + (side ? 3 : 0)));
+  const m3 I = ldm(L.IW(body));
+  v3 n = ld3(q + 6), t1, t2;
+  plane_space(n, t1, t2);
+  s.n = make_hrow(n, r, im, I, side);
+  s.t1 = make_hrow(t1, r, im, I, side);
+  s.t2 = make_hrow(t2, r, im, I, side);
+  s.trk = contact_target(P, q[9]) * s.n.rk;
+  s.in = q[10]; s.i1 = q[11]; s.i2 = q[12];
+  return s;
+}
+
+__device__ __forceinline__ int slot_points(const Lds& L, int sl) {   // contact points of slot sl (0: free, or past the last slot)
+  if (sl >= L.P->NS || L.POS()[sl] < 0) return 0;
+  return __float_as_int(L.MAN(sl)[0]);
+}
+
+__device__ __forceinline__ PSplit make_pair_split(const Lds& L, int tid) {
+  const DevParams& P = *L.P;
+  const int sl = tid >> 2, h = (tid >> 1) & 1;
+  const bool side = tid & 1;
+  PSplit p;
+  p.np = 0; p.colour = 0; p.pvw = L.VW(0);
+  p.mu = P.c.friction_rock * P.c.friction_rock;
+  int body = 0;
+  const float* mp = L.MAN(0);
+  if (sl < P.NS) {
+    const int pid = L.POS()[sl];
+    if (pid >= 0) {
+      int a, b; L.pair(pid, a, b);
+      body = side ? b : a;
+      mp = L.MAN(sl);
+      p.np = __float_as_int(mp[0]);
+      p.colour = L.COL()[sl];
+      p.pvw = L.VW(body);
+    }
+  }
+  p.s0 = make_hset(L, mp, 2 * h, p.np, body, side);
+  p.s1 = make_hset(L, mp, 2 * h + 1, p.np, body, side);
+  return p;
+}
+
+__device__ __forceinline__ void hrow_solve(const HRow& r, f2 (&u)[3], float trk, float& acc, float lo, float hi, float& res) {
+  const f2 s = fma2(r.k[0], u[0], fma2(r.k[1], u[1], r.k[2] * u[2]));   // A: (dot(d, va), dot(ca, wa)); B: minus its own
+  float own = s.x + s.y;
+  asm("" : "+v"(own));   // (kept from the vectoriser, as in prow_solve)
+  const float vrel = own + quad_partner(own);
+  float dl = fmaf(-vrel, r.rk, trk);
+  const float na = __builtin_amdgcn_fmed3f(acc + dl, lo, hi);
+  dl = na - acc;
+  acc = na;
+  res = fmaxf(res, fabsf(dl * r.kk));
+  const f2 d2 = F2(dl, dl);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) u[c] = fma2(r.u[c], d2, u[c]);
+}
+
+// A friction row's target rk = 0 rk (prow_solve forms the same product; its sign is rk's).  Off the chain, and formed where it is
+// used: as plain C++ the compiler hoists the four products of a lane out of the sweeps into registers the kernel does not have.
+__device__ __forceinline__ float zero_times(float rk) {
+  float t;
+  asm volatile("v_mul_f32 %0, 0, %1" : "=v"(t) : "v"(rk));
+  return t;
+}
+
+// one turn of a lane pair on one of its points: three rows on the two bodies' velocities, each in its lane's registers
+template <bool WARM>
+__device__ __forceinline__ void hset_turn(HSet& s, f2 (&u)[3], float mu, float ws, float& res) {
+  if (WARM) {
+    s.in = s.in * ws; s.i1 = s.i1 * ws; s.i2 = s.i2 * ws;
+    const f2 dn = F2(s.in, s.in), d1 = F2(s.i1, s.i1), d2 = F2(s.i2, s.i2);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) u[c] = fma2(s.n.u[c], dn, u[c]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) u[c] = fma2(s.t1.u[c], d1, u[c]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) u[c] = fma2(s.t2.u[c], d2, u[c]);
+  } else {
+    hrow_solve(s.n, u, s.trk, s.in, 0.0f, 1e30f, res);
+    const float lim = mu * s.in;
+    hrow_solve(s.t1, u, zero_times(s.t1.rk), s.i1, -lim, lim, res);
+    hrow_solve(s.t2, u, zero_times(s.t2.rk), s.i2, -lim, lim, res);
+  }
+}
+
+__device__ __forceinline__ void hvel_load(const float* p, f2 (&u)[3]) {
+  const float4 a0 = *(const float4*)p;
+  const float2 a1 = *(const float2*)(p + 4);
+  u[0] = F2(a0.x, a0.y); u[1] = F2(a0.z, a0.w); u[2] = F2(a1.x, a1.y);
+}
+__device__ __forceinline__ void hvel_store(float* p, const f2 (&u)[3]) {
+  *(float4*)p = make_float4(u[0].x, u[0].y, u[1].x, u[1].y); *(float2*)(p + 4) = make_float2(u[2].x, u[2].y);
+}
+
+// One colour's phase.  m1 / m2: the colour's lanes whose pair holds a first / a second point (a lane's pair: np > 2 h and
+// np > 2 h + 1), as wave-uniform masks.  Lanes (0, 1) of the quads, then lanes (2, 3); the phase ends at its first empty turn.
+// A pair's second turn runs inside its first's guard, on the velocities the first left in registers: one read and one write
+// of LDS per pair and phase.  (With a read and a write around every turn — the split alone — the headline shape gained
+// 10.6 %, with the velocities kept 14.5 %: profiles/pair_split_ab.txt.)
+template <bool WARM>
+__device__ __forceinline__ void pair_phase(PSplit& p, float ws, unsigned long long m1, unsigned long long m2, float& res) {
+  constexpr unsigned long long LO = 0x3333333333333333ull;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const unsigned long long t1 = m1 & (LO << (2 * h)), t2 = m2 & (LO << (2 * h));
+    if (t1 == 0) return;
+    if (__builtin_amdgcn_inverse_ballot_w64(t1)) {
+      f2 u[3];
+      hvel_load(p.pvw, u);
+      hset_turn<WARM>(p.s0, u, p.mu, ws, res);
+      if (t2 != 0) {
+        if (__builtin_amdgcn_inverse_ballot_w64(t2)) hset_turn<WARM>(p.s1, u, p.mu, ws, res);
+      }
+      hvel_store(p.pvw, u);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (t2 == 0) return;
+  }
+}
+
 // A wave runs only the turns it has points for (a turn no lane takes still costs a lone wave its control flow: 8 + 4 ncol empty
 // turns per sweep were a third of the sub-step's instructions in round 1; rounds 2 - 5 counted the turns per phase / per colour,
 // now a phase ends at its first empty mask).
@@ -854,14 +1031,19 @@ __device__ __forceinline__ void point_turn(const Lds& L, Point& p, float& res) {
 // (Bullet's m_leastSquaresResidual > m_leastSquaresResidualThreshold; the maximum over rows is order-independent, so
 // the parallel sweep decides exactly as the sequential definition).  The word of the other parity is the one the
 // next sweep writes, so a fast wave cannot disturb a slow wave's read.
+// PAIR_SPLIT (srl_k_step): a colour's phase is pair_phase — lanes (0, 1) of the colour's quads on their two points, then lanes
+// (2, 3) — under the same kind of scalar masks, made from the slot's point count and colour (a lane's own point does not exist:
+// both lanes of a pair must be in EXEC for a turn); solo and barrier sweeps share it.  8.22 against 9.42 ms per launch.
 // SOLO: every contact point of the env sits in wave 0 (the common case with few rocks: the ground points are the first
 // lanes, and manifold slots are handed out lowest first), so the sweep is wave 0's alone: the phases follow each other in
 // program order — the LDS serves one wave's accesses in order — without a single block barrier, and the residual is a
 // ballot.  The other waves skip the sweeps and wait at the barrier that ends the solve.
 template <bool WARM, int T, int PP, bool SOLO>
-__device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb, Point (&pp)[PP], int ncol, int gslot,
-                                             const int (&pslot)[PP], int gsweep, const unsigned long long (&cm)[2]) {
+__device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb, Point (&pp)[PP], PSplit& sp, int ncol, int gslot,
+                                             const int (&pslot)[PP], int gsweep, const unsigned long long (&cm)[2],
+                                             const unsigned long long (&cm2)[2]) {
   // gslot / pslot: the turn a lane's point takes (ground: its index; colour phases: 4 * colour + index; -1: none)
+  // PAIR_SPLIT: sp instead of pp / pslot; cm / cm2: the first two colours' lanes whose pair holds a first / a second point
   typedef Variant<T, PP> VA;
   static_assert(!SOLO || VA::SOLO, "a solo sweep in a variant that has none");
   float res = 0.0f;
@@ -890,6 +1072,9 @@ __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       if (c >= ncol) break;
+      if constexpr (VA::PAIR_SPLIT) {
+        pair_phase<WARM>(sp, L.P->c.warmstart, cm[c], cm2[c], res);
+      } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const unsigned long long t = cm[c] & (T0 << i);
@@ -897,12 +1082,18 @@ __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb
         if (__builtin_amdgcn_inverse_ballot_w64(t)) point_turn<WARM>(L, pp[0], res);
         __builtin_amdgcn_wave_barrier();
       }
+      }
     }
     c0 = 2;
   }
 #pragma unroll 1
   for (int c = c0; c < ncol; ++c) {
     if (!SOLO) __syncthreads();
+    if constexpr (VA::PAIR_SPLIT) {
+      const int h2 = (threadIdx.x >> 1) & 1;
+      const bool mine = sp.colour == c;
+      pair_phase<WARM>(sp, L.P->c.warmstart, __ballot(mine && sp.np > 2 * h2), __ballot(mine && sp.np > 2 * h2 + 1), res);
+    } else {
     unsigned long long mc[PP];
 #pragma unroll
     for (int r = 0; r < PP; ++r) mc[r] = __ballot((pslot[r] >> 2) == c);   // (pslot = -1: no point)
@@ -916,6 +1107,7 @@ __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb
       for (int r = 0; r < PP; ++r)
         if (__builtin_amdgcn_inverse_ballot_w64(mc[r] & (T0 << i))) point_turn<WARM>(L, pp[r], res);
       __builtin_amdgcn_wave_barrier();
+    }
     }
   }
   if (SOLO) return WARM ? true : __ballot(res * res > L.P->c.residual_threshold) != 0ull;
@@ -941,7 +1133,9 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
   // With two contact points per thread the register file is full: lane-dependent LDS addresses that the compiler
   // hoists out of the sub-step loop end up spilled to scratch and are reloaded from memory in every sub-step.  An
   // opaque copy of the thread index keeps them inside the loop, where recomputing one costs an instruction or two.
-  if (PP >= 2) asm volatile("" : "+v"(tid));
+  // The same with the pair split's two register sets per lane: 40 spill stores / reloads and 116 bytes of scratch without
+  // it, none with it (the parent had 8 and 68 bytes); the launch time is the same either way (profiles/pair_split_ab.txt).
+  if (PP >= 2 || VA::PAIR_SPLIT) asm volatile("" : "+v"(tid));
 #ifdef SRL_STAMPS
   long long _t0 = wall_clock64();
 #endif
@@ -1037,8 +1231,14 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
     GPoint gp = make_ground_point(L, tid / SRL_GMAXP, tid % SRL_GMAXP);
     if (tid / SRL_GMAXP >= nb) gp.valid = false;
     Point pp[PP];
+    PSplit sp;
+    if constexpr (VA::PAIR_SPLIT) {   // (of pp only `valid` is read below: the lane's slot holds points; sp is made once gp is dead)
+#pragma unroll
+      for (int r = 0; r < PP; ++r) pp[r].valid = slot_points(L, tid >> 2) > 0;
+    } else {
 #pragma unroll
     for (int r = 0; r < PP; ++r) pp[r] = make_pair_point(L, (tid + r * T) >> 2, tid & 3);
+    }
     {   // a wave other than the first that holds a contact point rules the solo sweep out
       bool mine = gp.valid;
 #pragma unroll
@@ -1066,15 +1266,26 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
     }
     __syncthreads();   // the records are in LDS
     }
+    if constexpr (VA::PAIR_SPLIT) sp = make_pair_split(L, tid);
     STAMP(5);
     const bool solo = VA::SOLO && misc[M_SOLO] != 0;
     const int gslot = gp.valid ? gp.idx : -1;
     // the lanes of the first two colours (solo sweeps: solver_sweep)
-    unsigned long long cm[2];
-    cm[0] = __ballot(pp[0].valid && pp[0].colour == 0); cm[1] = __ballot(pp[0].valid && pp[0].colour == 1);
+    unsigned long long cm[2], cm2[2] = {0ull, 0ull};
     int pslot[PP];
+    if constexpr (VA::PAIR_SPLIT) {
+      const int h2 = (tid >> 1) & 1;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        cm[c] = __ballot(sp.colour == c && sp.np > 2 * h2); cm2[c] = __ballot(sp.colour == c && sp.np > 2 * h2 + 1);
+      }
+#pragma unroll
+      for (int r = 0; r < PP; ++r) pslot[r] = -1;
+    } else {
+    cm[0] = __ballot(pp[0].valid && pp[0].colour == 0); cm[1] = __ballot(pp[0].valid && pp[0].colour == 1);
 #pragma unroll
     for (int r = 0; r < PP; ++r) pslot[r] = pp[r].valid ? 4 * pp[r].colour + pp[r].idx : -1;
+    }
     // at most solver_iterations sweeps, ended early once a sweep's largest squared residual is <= the threshold
     // (btSequentialImpulseConstraintSolver::solveGroupCacheFriendlyIterations)
     if (solo) {
@@ -1101,10 +1312,10 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
           }
           if (gb.np > 0) { *(float4*)gb.pvw = make_float4(v.x, w.x, v.y, w.y); *(float2*)(gb.pvw + 4) = make_float2(v.z, w.z); }
         } else {
-          solver_sweep<true, T, PP, VA::SOLO>(L, gp, gb, pp, ncol, gslot, pslot, 0, cm);
+          solver_sweep<true, T, PP, VA::SOLO>(L, gp, gb, pp, sp, ncol, gslot, pslot, 0, cm, cm2);
           for (int it = 0; it < P.c.solver_iterations; ++it) {
             done++;
-            if (!solver_sweep<false, T, PP, VA::SOLO>(L, gp, gb, pp, ncol, gslot, pslot, 0, cm)) break;
+            if (!solver_sweep<false, T, PP, VA::SOLO>(L, gp, gb, pp, sp, ncol, gslot, pslot, 0, cm, cm2)) break;
           }
         }
         if (tid == 0) misc[M_CNT] = done;   // (M_CNT is free between the calls of newest_contacts)
@@ -1112,10 +1323,10 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
       __syncthreads();
       gsweep += misc[M_CNT];
     } else {
-      solver_sweep<true, T, PP, false>(L, gp, gb, pp, ncol, gslot, pslot, 0, cm);
+      solver_sweep<true, T, PP, false>(L, gp, gb, pp, sp, ncol, gslot, pslot, 0, cm, cm2);
       for (int it = 0; it < P.c.solver_iterations; ++it) {
         gsweep++;
-        if (!solver_sweep<false, T, PP, false>(L, gp, gb, pp, ncol, gslot, pslot, gsweep, cm)) break;
+        if (!solver_sweep<false, T, PP, false>(L, gp, gb, pp, sp, ncol, gslot, pslot, gsweep, cm, cm2)) break;
       }
     }
 #ifdef SRL_STAMPS
@@ -1155,12 +1366,21 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
       for (int i = 0; i < SRL_GMAXP; ++i)
         if (i < gb.np) { g[SRL_GM_IN + i] = gb.acc[i][0]; g[SRL_GM_T1 + i] = gb.acc[i][1]; g[SRL_GM_T2 + i] = gb.acc[i][2]; }
     }
+    if constexpr (VA::PAIR_SPLIT) {   // the A lane of a pair writes its two points
+      const int i0 = tid & 2;
+      if (!(tid & 1) && sp.np > i0) {
+        float* q = L.MAN(tid >> 2) + 4 + SRL_MP_WORDS * i0;
+        q[10] = sp.s0.in; q[11] = sp.s0.i1; q[12] = sp.s0.i2;
+        if (sp.np > i0 + 1) { q[SRL_MP_WORDS + 10] = sp.s1.in; q[SRL_MP_WORDS + 11] = sp.s1.i1; q[SRL_MP_WORDS + 12] = sp.s1.i2; }
+      }
+    } else {
 #pragma unroll
     for (int r = 0; r < PP; ++r)
       if (pp[r].valid) {
         float* q = L.MAN((tid + r * T) >> 2) + 4 + SRL_MP_WORDS * pp[r].idx;
         q[10] = pp[r].in; q[11] = pp[r].i1; q[12] = pp[r].i2;
       }
+    }
   }
   STAMP(6);
   // (7) integrate (the last solver phase ended with a barrier)
@@ -1515,6 +1735,10 @@ struct Variant {
   // sweeps by wave 0 alone while it holds every contact point (solver_sweep<SOLO>): the variants with two points per thread
   // are out of registers as it is
   static constexpr bool SOLO = PP == 1;
+  // a pair contact solved on two lanes, one per body (pair_phase), in the two-wave variant of <= 8 rocks: a launch there lasts
+  // as long as one wave's dependent chain, and a turn is 67 -> 45 vector instructions — 9.42 -> 8.22 ms per launch at the
+  // headline shape; the other three are throughput-bound and out of registers (profiles/pair_split_experiment.md)
+  static constexpr bool PAIR_SPLIT = T == 128 && PP == 1;
 };
 
 extern "C" __global__ void __launch_bounds__(128, 2) srl_k_step(const DevParams* __restrict__ Pp,
