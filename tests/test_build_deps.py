@@ -34,6 +34,7 @@ def test_the_derived_set_is_the_compilers(name):
   assert build.deps(name) == _compiler_deps(name)
   if name == 'env':
     assert os.path.join('stackrl_amd', 'csrc', 'stage.h') in build.deps('env')
+    assert os.path.join('stackrl_amd', 'csrc', 'solver.h') in build.deps('env')
 
 
 def _copy(tmp_path):
