@@ -16,19 +16,16 @@
 //   epilogue: bias + ReLU on the 4 consecutive channels a lane holds, 8-byte stores into a channel slice of a
 //   channels-last buffer.
 // bf16 in / out with fp32 accumulation; the fp32-class variant (float32 in / out, bf16x3 products) splits the staged
-// tile into hi / lo planes like k_conv3x3_x3.
+// tile into hi / lo planes like k_conv3x3_x3 (the split, the three-product MFMA and the bias + ReLU: csrc/mfma_bf16.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/stackrl_qnet.h"
-#include "srl_bf16.h"
+#include "mfma_bf16.h"
+#include "srl_error.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 
 template <int COUT, int W, bool X3 = false>
 struct GemmCfg {
@@ -112,13 +109,11 @@ k_conv3x3_gemm(const void* __restrict__ in_, const uint16_t* __restrict__ wfrag,
           const float* s = (const float*)in_ + src;
           float4 a = *(const float4*)s, c = *(const float4*)(s + 4);
           if (!ok) { a = make_float4(0.0f, 0.0f, 0.0f, 0.0f); c = a; }
-          const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-          uint32_t hi[4], lo[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) srl_split_bf16(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
+          uint4 hi, lo;
+          SRL_SPLIT8(a, c, hi, lo)
           const int slot = G::SWZ ? (ch ^ ((cc >> 2) & 3)) : ch;
-          *(uint4*)(tile + p * G::PS + slot * 8) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-          *(uint4*)(tile + G::TILE + p * G::PS + slot * 8) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+          *(uint4*)(tile + p * G::PS + slot * 8) = hi;
+          *(uint4*)(tile + G::TILE + p * G::PS + slot * 8) = lo;
         } else {
           uint4 v = *(const uint4*)((const uint16_t*)in_ + src);
           if (!ok) v = make_uint4(0u, 0u, 0u, 0u);
@@ -161,11 +156,7 @@ k_conv3x3_gemm(const void* __restrict__ in_, const uint16_t* __restrict__ wfrag,
         __builtin_amdgcn_sched_barrier(0);
         if (X3) {
 #pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], xh, acc[mt][t], 0, 0, 0);
-            acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xl, acc[mt][t], 0, 0, 0);
-            acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xh, acc[mt][t], 0, 0, 0);
-          }
+          for (int mt = 0; mt < 4; ++mt) SRL_MFMA_X3(acc[mt][t], ah[mt], al[mt], xh, xl)
         } else {
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt) acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xh, acc[mt][t], 0, 0, 0);
@@ -189,11 +180,9 @@ k_conv3x3_gemm(const void* __restrict__ in_, const uint16_t* __restrict__ wfrag,
       const int p = wn * 128 + t * 16 + n;
       const int im = p / (G::RT * W), r = (p / W) % G::RT, c = p % W;
       const size_t pix = ((size_t)(img0 + im) * W + row0 + r) * W + c;
-      const float v0 = fmaxf(acc[mt][t][0] + bz.x, 0.0f), v1 = fmaxf(acc[mt][t][1] + bz.y, 0.0f);
-      const float v2 = fmaxf(acc[mt][t][2] + bz.z, 0.0f), v3 = fmaxf(acc[mt][t][3] + bz.w, 0.0f);
-      if (X3) *(float4*)((float*)out_ + pix * ostride + ooff + co) = make_float4(v0, v1, v2, v3);
-      else *(uint2*)((uint16_t*)out_ + pix * ostride + ooff + co) =
-             make_uint2(srl_pk_bf16(v0, v1), srl_pk_bf16(v2, v3));
+      const float4 v = SRL_BIAS_RELU(acc[mt][t], bz);
+      if (X3) *(float4*)((float*)out_ + pix * ostride + ooff + co) = v;
+      else *(uint2*)((uint16_t*)out_ + pix * ostride + ooff + co) = make_uint2(srl_pk_bf16(v.x, v.y), srl_pk_bf16(v.z, v.w));
     }
   }
 }
@@ -237,22 +226,16 @@ k_convt2x2_gemm(const void* __restrict__ in_, const uint16_t* __restrict__ wfrag
       if (X3) {
         const float* s = (const float*)in_ + p * CIN + 32 * ks + 8 * g;
         const float4 a = *(const float4*)s, c = *(const float4*)(s + 4);
-        const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-        uint32_t ph[4], pl[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) srl_split_bf16(v[2 * j], v[2 * j + 1], ph[j], pl[j]);
-        xh = __builtin_bit_cast(bf16x8, make_uint4(ph[0], ph[1], ph[2], ph[3]));
-        xl = __builtin_bit_cast(bf16x8, make_uint4(pl[0], pl[1], pl[2], pl[3]));
+        uint4 ph, pl;
+        SRL_SPLIT8(a, c, ph, pl)
+        xh = __builtin_bit_cast(bf16x8, ph); xl = __builtin_bit_cast(bf16x8, pl);
       } else {
         xh = *(const bf16x8*)((const uint16_t*)in_ + p * CIN + 32 * ks + 8 * g);
       }
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
-        if (X3) {
-          acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], xh, acc[mt][t], 0, 0, 0);
-          acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xl, acc[mt][t], 0, 0, 0);
-        }
-        acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xh, acc[mt][t], 0, 0, 0);
+        if (X3) SRL_MFMA_X3(acc[mt][t], ah[mt], al[mt], xh, xl)
+        else acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], xh, acc[mt][t], 0, 0, 0);
       }
     }
   }
@@ -268,11 +251,10 @@ k_convt2x2_gemm(const void* __restrict__ in_, const uint16_t* __restrict__ wfrag
       const int m = 64 * mb + 16 * mt + 4 * g;          // row of the GEMM = (dy, dx, co)
       const int q = m / COUT, co = m - q * COUT, dy = q >> 1, dx = q & 1;
       const float4 bz = *(const float4*)(bias + co);
-      const float v0 = fmaxf(acc[mt][t][0] + bz.x, 0.0f), v1 = fmaxf(acc[mt][t][1] + bz.y, 0.0f);
-      const float v2 = fmaxf(acc[mt][t][2] + bz.z, 0.0f), v3 = fmaxf(acc[mt][t][3] + bz.w, 0.0f);
+      const float4 v = SRL_BIAS_RELU(acc[mt][t], bz);
       const size_t o = (((size_t)b * 2 * H + 2 * y + dy) * 2 * W + 2 * x + dx) * ostride + ooff + co;
-      if (X3) *(float4*)((float*)out_ + o) = make_float4(v0, v1, v2, v3);
-      else *(uint2*)((uint16_t*)out_ + o) = make_uint2(srl_pk_bf16(v0, v1), srl_pk_bf16(v2, v3));
+      if (X3) *(float4*)((float*)out_ + o) = v;
+      else *(uint2*)((uint16_t*)out_ + o) = make_uint2(srl_pk_bf16(v.x, v.y), srl_pk_bf16(v.z, v.w));
     }
   }
 }
@@ -291,9 +273,7 @@ int launch_gemm(const void* in, const void* wfrag, const float* bias, void* out,
   }
   hipLaunchKernelGGL((k_conv3x3_gemm<CIN, COUT, W, X3>), dim3(nwg), dim3(256), lds, st, in, (const uint16_t*)wfrag, bias, out,
                      ostride, ooff);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(gm_err, sizeof gm_err, "srl_conv3x3_gemm: %s", hipGetErrorString(e)); return 2; }
-  return 0;
+  return launched(gm_err, "srl_conv3x3_gemm");
 }
 
 template <bool X3>
@@ -371,9 +351,7 @@ int srl_convt2x2_gemm_bias_relu(const void* in, const void* wfrag, const float* 
   }
   SRL_CT(128, 64) SRL_CT(256, 128)
 #undef SRL_CT
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(gm_err, sizeof gm_err, "srl_convt2x2_gemm_bias_relu: %s", hipGetErrorString(e)); return 2; }
-  return 0;
+  return launched(gm_err, "srl_convt2x2_gemm_bias_relu");
 }
 
 }  // extern "C"

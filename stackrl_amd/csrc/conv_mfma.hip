@@ -15,17 +15,19 @@
 //   epilogue: bias + ReLU on the 4 consecutive output channels a lane holds, 8-byte stores into a channel slice of a
 //   channels-last buffer (the decoder's concat buffer), optionally the 2 x 2 max-pooled tensor too (rows in registers,
 //   columns by a DPP quad permute), or channel-major output for the cross-correlation.
+// Shared with csrc/conv_gemm.hip through csrc/mfma_bf16.h: the fragment types, the fp32-class operand split and three-product
+// MFMA, the bias + ReLU of a lane's four channels.  The bf16 and the fp32-class export of a layer kind share one host body
+// (check, then dispatch); refusals and launch errors end in csrc/srl_error.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/stackrl_qnet.h"
-#include "srl_bf16.h"
+#include "mfma_bf16.h"
+#include "srl_error.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // The four lane groups of a wave hold the four channel quarters of one pixel: (q0 + q1) + (q2 + q3) into lane group 0 (the
@@ -147,9 +149,8 @@ k_conv3x3(const uint16_t* __restrict__ in, const uint16_t* __restrict__ wfrag, c
     uint32_t lo[RW], hi[RW];   // packed bf16 pairs per row
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
-      const float v0 = fmaxf(acc[r][mt][0] + bz.x, 0.0f), v1 = fmaxf(acc[r][mt][1] + bz.y, 0.0f);
-      const float v2 = fmaxf(acc[r][mt][2] + bz.z, 0.0f), v3 = fmaxf(acc[r][mt][3] + bz.w, 0.0f);
-      lo[r] = srl_pk_bf16(v0, v1); hi[r] = srl_pk_bf16(v2, v3);
+      const float4 v = SRL_BIAS_RELU(acc[r][mt], bz);
+      lo[r] = srl_pk_bf16(v.x, v.y); hi[r] = srl_pk_bf16(v.z, v.w);
       const int y = y0 + row0 + r, x = x0 + n;
       if (nchw) {
         uint16_t* o = out + ((size_t)b * COUT + co) * H * W + (size_t)y * W + x;
@@ -230,8 +231,7 @@ __device__ __forceinline__ void x3_epilogue(const f32x4 (&acc)[RW][MT_W], const 
     float4 val[RW];
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
-      val[r] = make_float4(fmaxf(acc[r][mt][0] + bz.x, 0.0f), fmaxf(acc[r][mt][1] + bz.y, 0.0f),
-                           fmaxf(acc[r][mt][2] + bz.z, 0.0f), fmaxf(acc[r][mt][3] + bz.w, 0.0f));
+      val[r] = SRL_BIAS_RELU(acc[r][mt], bz);
       const int y = y0 + row0 + r, x = x0 + n;
       if (nchw) {
         float* o = out + ((size_t)b * COUT + co) * H * W + (size_t)y * W + x;
@@ -336,11 +336,7 @@ __device__ __forceinline__ void x3_mfma_pass(const uint16_t* tile, int plane, in
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int mt = 0; mt < MT_W; ++mt) {
-        acc[r][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[ks][mt], xh, acc[r][mt], 0, 0, 0);
-        acc[r][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][mt], xl, acc[r][mt], 0, 0, 0);
-        acc[r][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][mt], xh, acc[r][mt], 0, 0, 0);
-      }
+      for (int mt = 0; mt < MT_W; ++mt) SRL_MFMA_X3(acc[r][mt], wh[ks][mt], wl[ks][mt], xh, xl)
       xh = yh; xl = yl;
     }
     off = offn;
@@ -620,51 +616,13 @@ k_thin_conv3x3_x3(const TIN* __restrict__ in, const float* __restrict__ w1, cons
 // 16 bytes) come straight from global memory.  Wave = 16 consecutive input pixels of a row x all M tiles; weights
 // packed in A-fragment order and register-resident; output written into a channel slice of the channels-last
 // concat buffer (8 bytes per lane: 4 consecutive channels of one output pixel).
-template <int CIN, int COUT>
+// X3: the fp32-class form (float32 in and out, bf16x3 products like k_conv3x3_x3): the lane's 8 input channels (32 bytes) are
+// split into hi / lo parts in registers, the weights arrive pre-split (hi fragments, then lo fragments; 128 VGPRs for
+// 64 -> 32); 16-byte stores of 4 consecutive output channels.
+template <int CIN, int COUT, bool X3>
 __global__ void __launch_bounds__(256, 2)
-k_convt2x2(const uint16_t* __restrict__ in, const uint16_t* __restrict__ wfrag, const float* __restrict__ bias,
-           uint16_t* __restrict__ out, int H, int W, int ostride, int ooff, long long ntiles) {
-  constexpr int MT = 4 * COUT / 16, KS = CIN / 32;
-  const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
-  bf16x8 wf[KS][MT];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) wf[ks][mt] = ((const bf16x8*)wfrag)[(ks * MT + mt) * 64 + lane];
-  const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // 16 consecutive input pixels (W % 16 == 0)
-  if (tile >= ntiles) return;
-  const long long pix0 = tile * 16;
-  f32x4 acc[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const bf16x8 xf = *(const bf16x8*)(in + (pix0 + n) * CIN + 32 * ks + 8 * g);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][mt], xf, acc[mt], 0, 0, 0);
-  }
-  const long long p = pix0 + n;
-  const int x = (int)(p % W);
-  const long long by = p / W;          // b * H + y
-  const long long b = by / H; const int y = (int)(by - b * H);
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int m = 16 * mt + 4 * g;     // row of the GEMM = (dy, dx, co)
-    const int q = m / COUT, co = m - q * COUT, dy = q >> 1, dx = q & 1;
-    const float4 bz = *(const float4*)(bias + co);
-    const uint32_t lo = srl_pk_bf16(fmaxf(acc[mt][0] + bz.x, 0.0f), fmaxf(acc[mt][1] + bz.y, 0.0f));
-    const uint32_t hi = srl_pk_bf16(fmaxf(acc[mt][2] + bz.z, 0.0f), fmaxf(acc[mt][3] + bz.w, 0.0f));
-    *(uint2*)(out + (((b * 2 * H + 2 * y + dy) * 2 * W) + 2 * x + dx) * ostride + ooff + co) = make_uint2(lo, hi);
-  }
-}
-
-// The transposed convolution in fp32-class precision (float32 in and out, bf16x3 products like k_conv3x3_x3): the lane's
-// 8 input channels (32 bytes) are split into hi / lo parts in registers, the weights arrive pre-split (hi fragments, then
-// lo fragments; 128 VGPRs for 64 -> 32); 16-byte stores of 4 consecutive output channels.
-template <int CIN, int COUT>
-__global__ void __launch_bounds__(256, 2)
-k_convt2x2_x3(const float* __restrict__ in, const uint16_t* __restrict__ wfrag, const float* __restrict__ bias,
-              float* __restrict__ out, int H, int W, int ostride, int ooff, long long ntiles) {
+k_convt2x2(const void* __restrict__ in_, const uint16_t* __restrict__ wfrag, const float* __restrict__ bias,
+           void* __restrict__ out_, int H, int W, int ostride, int ooff, long long ntiles) {
   constexpr int MT = 4 * COUT / 16, KS = CIN / 32;
   const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
   bf16x8 wh[KS][MT], wl[KS][MT];
@@ -673,7 +631,7 @@ k_convt2x2_x3(const float* __restrict__ in, const uint16_t* __restrict__ wfrag, 
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       wh[ks][mt] = ((const bf16x8*)wfrag)[(ks * MT + mt) * 64 + lane];
-      wl[ks][mt] = ((const bf16x8*)wfrag)[((KS + ks) * MT + mt) * 64 + lane];
+      if (X3) wl[ks][mt] = ((const bf16x8*)wfrag)[((KS + ks) * MT + mt) * 64 + lane];
     }
   const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // 16 consecutive input pixels (W % 16 == 0)
   if (tile >= ntiles) return;
@@ -683,19 +641,20 @@ k_convt2x2_x3(const float* __restrict__ in, const uint16_t* __restrict__ wfrag, 
   for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    const float* src = in + (pix0 + n) * CIN + 32 * ks + 8 * g;
-    const float4 a = *(const float4*)src, c = *(const float4*)(src + 4);
-    const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-    uint32_t ph[4], pl[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) srl_split_bf16(v[2 * j], v[2 * j + 1], ph[j], pl[j]);
-    const bf16x8 xh = __builtin_bit_cast(bf16x8, make_uint4(ph[0], ph[1], ph[2], ph[3]));
-    const bf16x8 xl = __builtin_bit_cast(bf16x8, make_uint4(pl[0], pl[1], pl[2], pl[3]));
+    bf16x8 xh, xl;
+    if (X3) {
+      const float* src = (const float*)in_ + (pix0 + n) * CIN + 32 * ks + 8 * g;
+      const float4 a = *(const float4*)src, c = *(const float4*)(src + 4);
+      uint4 ph, pl;
+      SRL_SPLIT8(a, c, ph, pl)
+      xh = __builtin_bit_cast(bf16x8, ph); xl = __builtin_bit_cast(bf16x8, pl);
+    } else {
+      xh = *(const bf16x8*)((const uint16_t*)in_ + (pix0 + n) * CIN + 32 * ks + 8 * g);
+    }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[ks][mt], xh, acc[mt], 0, 0, 0);
-      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][mt], xl, acc[mt], 0, 0, 0);
-      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][mt], xh, acc[mt], 0, 0, 0);
+      if (X3) SRL_MFMA_X3(acc[mt], wh[ks][mt], wl[ks][mt], xh, xl)
+      else acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][mt], xh, acc[mt], 0, 0, 0);
     }
   }
   const long long p = pix0 + n;
@@ -707,75 +666,117 @@ k_convt2x2_x3(const float* __restrict__ in, const uint16_t* __restrict__ wfrag, 
     const int m = 16 * mt + 4 * g;     // row of the GEMM = (dy, dx, co)
     const int q = m / COUT, co = m - q * COUT, dy = q >> 1, dx = q & 1;
     const float4 bz = *(const float4*)(bias + co);
-    store_f4(out + (((b * 2 * H + 2 * y + dy) * 2 * W) + 2 * x + dx) * ostride + ooff + co, fmaxf(acc[mt][0] + bz.x, 0.0f),
-             fmaxf(acc[mt][1] + bz.y, 0.0f), fmaxf(acc[mt][2] + bz.z, 0.0f), fmaxf(acc[mt][3] + bz.w, 0.0f));
+    // (each store in the statement order it was tuned in — bf16: the values, then the address; float32: the address first;
+    // either swap reorders the instructions of k_convt2x2<64, 32, *>, profiles/rollout_conv_refactor.txt)
+    if (X3) {
+      float* o = (float*)out_ + (((b * 2 * H + 2 * y + dy) * 2 * W) + 2 * x + dx) * ostride + ooff + co;
+      const float4 v = SRL_BIAS_RELU(acc[mt], bz);
+      store_f4(o, v.x, v.y, v.z, v.w);
+    } else {
+      const uint32_t lo = srl_pk_bf16(fmaxf(acc[mt][0] + bz.x, 0.0f), fmaxf(acc[mt][1] + bz.y, 0.0f));
+      const uint32_t hi = srl_pk_bf16(fmaxf(acc[mt][2] + bz.z, 0.0f), fmaxf(acc[mt][3] + bz.w, 0.0f));
+      *(uint2*)((uint16_t*)out_ + (((b * 2 * H + 2 * y + dy) * 2 * W) + 2 * x + dx) * ostride + ooff + co) = make_uint2(lo, hi);
+    }
   }
 }
 
 thread_local char c_err[256] = "";
 
-template <int CIN, int COUT>
-int launch(const void* in, const void* wfrag, const float* bias, void* out, void* pooled, int B, int H, int W, int ostride,
-           int ooff, int nchw, hipStream_t st) {
-  const size_t lds = sizeof(uint16_t) * ConvCfg<CIN>::TW * ConvCfg<CIN>::TW * ConvCfg<CIN>::PS;
-  constexpr int MT_W = CIN >= 64 ? 1 : COUT / 16;
-  hipLaunchKernelGGL((k_conv3x3<CIN, COUT, MT_W, false>), dim3((W / 16) * (H / 16), B), dim3(256), lds, st, (const uint16_t*)in,
-                     (const uint16_t*)wfrag, bias, (uint16_t*)out, (uint16_t*)pooled, H, W, ostride, ooff, nchw,
-                     (const float*)nullptr, 0.0f, (float*)nullptr, 0, 0);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(c_err, sizeof c_err, "srl_conv3x3_bias_relu: %s", hipGetErrorString(e)); return 2; }
-  return 0;
+// bytes of the LDS tile of CB channels: one plane, or (fp32-class) the hi and the lo plane
+template <int CB>
+constexpr size_t tile_lds(bool x3) { return (x3 ? 2 : 1) * sizeof(uint16_t) * ConvCfg<CB>::TW * ConvCfg<CB>::TW * ConvCfg<CB>::PS; }
+
+template <bool X3, int CIN, int COUT>
+int launch(const char* what, const void* in, const void* wfrag, const float* bias, void* out, void* pooled, int B, int H, int W,
+           int ostride, int ooff, int nchw, hipStream_t st) {
+  const dim3 grid((W / 16) * (H / 16), B), blk(256);
+  if constexpr (X3)   // 64 input channels: two passes of 32
+    hipLaunchKernelGGL((k_conv3x3_x3<CIN, COUT, COUT / 16, false>), grid, blk, tile_lds<(CIN > 32 ? 32 : CIN)>(true), st, (const float*)in,
+                       (const uint16_t*)wfrag, bias, (float*)out, (float*)pooled, H, W, ostride, ooff, nchw, (const float*)nullptr,
+                       0.0f, (float*)nullptr, 0, 0);
+  else
+    hipLaunchKernelGGL((k_conv3x3<CIN, COUT, (CIN >= 64 ? 1 : COUT / 16), false>), grid, blk, tile_lds<CIN>(false), st,
+                       (const uint16_t*)in, (const uint16_t*)wfrag, bias, (uint16_t*)out, (uint16_t*)pooled, H, W, ostride, ooff, nchw,
+                       (const float*)nullptr, 0.0f, (float*)nullptr, 0, 0);
+  return launched(c_err, what);
 }
 
-template <int CIN, int COUT>
-int launch_x3(const float* in, const void* wfrag, const float* bias, float* out, float* pooled, int B, int H, int W, int ostride,
-              int ooff, int nchw, hipStream_t st) {
-  typedef ConvCfg<(CIN > 32 ? 32 : CIN)> G;   // 64 input channels: two passes of 32
-  const size_t lds = 2 * sizeof(uint16_t) * G::TW * G::TW * G::PS;
-  constexpr int MT_W = COUT / 16;
-  hipLaunchKernelGGL((k_conv3x3_x3<CIN, COUT, MT_W, false>), dim3((W / 16) * (H / 16), B), dim3(256), lds, st, in, (const uint16_t*)wfrag,
-                     bias, out, pooled, H, W, ostride, ooff, nchw, (const float*)nullptr, 0.0f, (float*)nullptr, 0, 0);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(c_err, sizeof c_err, "srl_conv3x3_bias_relu_f32: %s", hipGetErrorString(e)); return 2; }
-  return 0;
+// srl_conv3x3_bias_relu (X3: _f32): the check, then the (cin, cout) ladder of the tile kernels
+template <bool X3>
+int conv3x3(const char* what, const void* in, const void* wfrag, const float* bias, void* out, void* pooled, int B, int H, int W,
+            int cin, int cout, int ostride, int ooff, int nchw, hipStream_t st) {
+  if (!in || !wfrag || !bias || !out || B < 1 || H < 16 || W < 16 || H % 16 || W % 16 || ostride % 4 || ooff % 4 ||
+      srl_conv3x3_wfrag_elems(cin, cout) < 0 || (pooled && nchw))
+    return refused(c_err, what, " (H, W multiples of 16; cin in {16, 32, 64}, cout in {16, 32})");
+#define SRL_CASE(CI, CO) if (cin == CI && cout == CO) return launch<X3, CI, CO>(what, in, wfrag, bias, out, pooled, B, H, W, ostride, ooff, nchw, st);
+  SRL_CASE(16, 16) SRL_CASE(16, 32) SRL_CASE(32, 16) SRL_CASE(32, 32) SRL_CASE(64, 16)
+#undef SRL_CASE
+  return launch<X3, 64, 32>(what, in, wfrag, bias, out, pooled, B, H, W, ostride, ooff, nchw, st);
 }
+
+// the four (cin, in_dtype) forms of the thin layer's input: LAUNCH(channels, element type)
+#define SRL_THIN_INPUT(LAUNCH) \
+  if (cin == 1 && in_dtype == 0) LAUNCH(1, uint8_t); \
+  else if (cin == 1) LAUNCH(1, float); \
+  else if (in_dtype == 0) LAUNCH(2, uint8_t); \
+  else LAUNCH(2, float);
 
 template <typename TOUT>
 int launch_thin(const char* what, const void* in, int32_t in_dtype, const float* w, const float* bias, TOUT* o, int32_t B,
                 int32_t H, int32_t W, int32_t cin, int32_t Hp, int32_t Wp, hipStream_t st) {
   if (!in || !w || !bias || !o || B < 1 || H < 1 || W < 1 || Hp < H || Wp < W || (cin != 1 && cin != 2) ||
-      (in_dtype != 0 && in_dtype != 1)) {
-    snprintf(c_err, sizeof c_err, "%s: bad arguments (cin in {1, 2}; in_dtype 0 = uint8 / 255, 1 = float32)", what);
-    return 1;
-  }
+      (in_dtype != 0 && in_dtype != 1))
+    return refused(c_err, what, " (cin in {1, 2}; in_dtype 0 = uint8 / 255, 1 = float32)");
   const dim3 grid((H * W + 255) / 256, B), blk(256);
-  if (cin == 1 && in_dtype == 0) hipLaunchKernelGGL((k_conv3x3_thin<1, uint8_t, TOUT>), grid, blk, 0, st, (const uint8_t*)in, w, bias, o, H, W, Hp, Wp);
-  else if (cin == 1) hipLaunchKernelGGL((k_conv3x3_thin<1, float, TOUT>), grid, blk, 0, st, (const float*)in, w, bias, o, H, W, Hp, Wp);
-  else if (in_dtype == 0) hipLaunchKernelGGL((k_conv3x3_thin<2, uint8_t, TOUT>), grid, blk, 0, st, (const uint8_t*)in, w, bias, o, H, W, Hp, Wp);
-  else hipLaunchKernelGGL((k_conv3x3_thin<2, float, TOUT>), grid, blk, 0, st, (const float*)in, w, bias, o, H, W, Hp, Wp);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(c_err, sizeof c_err, "%s: %s", what, hipGetErrorString(e)); return 2; }
-  return 0;
+#define SRL_THIN(CT, TIN) hipLaunchKernelGGL((k_conv3x3_thin<CT, TIN, TOUT>), grid, blk, 0, st, (const TIN*)in, w, bias, o, H, W, Hp, Wp)
+  SRL_THIN_INPUT(SRL_THIN)
+#undef SRL_THIN
+  return launched(c_err, what);
 }
 
 template <bool PROJ>
 int launch_thin_conv(const char* what, const void* in, int32_t in_dtype, int32_t cin, const float* w1, const float* b1, const void* wfrag,
                      const float* bias, float* out, float* pooled, int B, int H, int W, int ostride, int ooff, int nchw,
                      const float* pw, float pb, float* proj_out, hipStream_t st) {
-  const size_t lds = 2 * sizeof(uint16_t) * ConvCfg<16>::TW * ConvCfg<16>::TW * ConvCfg<16>::PS;
   const dim3 grid(((W + 15) / 16) * ((H + 15) / 16), B), blk(256);
-  const uint16_t* wf = (const uint16_t*)wfrag;
-  if (cin == 1 && in_dtype == 0)
-    hipLaunchKernelGGL((k_thin_conv3x3_x3<1, uint8_t, PROJ>), grid, blk, lds, st, (const uint8_t*)in, w1, b1, wf, bias, out, pooled, H, W, ostride, ooff, nchw, pw, pb, proj_out);
-  else if (cin == 1)
-    hipLaunchKernelGGL((k_thin_conv3x3_x3<1, float, PROJ>), grid, blk, lds, st, (const float*)in, w1, b1, wf, bias, out, pooled, H, W, ostride, ooff, nchw, pw, pb, proj_out);
-  else if (in_dtype == 0)
-    hipLaunchKernelGGL((k_thin_conv3x3_x3<2, uint8_t, PROJ>), grid, blk, lds, st, (const uint8_t*)in, w1, b1, wf, bias, out, pooled, H, W, ostride, ooff, nchw, pw, pb, proj_out);
+#define SRL_THIN(CT, TIN) \
+  hipLaunchKernelGGL((k_thin_conv3x3_x3<CT, TIN, PROJ>), grid, blk, tile_lds<16>(true), st, (const TIN*)in, w1, b1, (const uint16_t*)wfrag, \
+                     bias, out, pooled, H, W, ostride, ooff, nchw, pw, pb, proj_out)
+  SRL_THIN_INPUT(SRL_THIN)
+#undef SRL_THIN
+  return launched(c_err, what);
+}
+#undef SRL_THIN_INPUT
+
+// srl_convt2x2_bias_relu (X3: _f32)
+template <bool X3>
+int convt2x2(const char* what, const void* in, const void* wfrag, const float* bias, void* out, int B, int H, int W, int cin, int cout,
+             int ostride, int ooff, hipStream_t st) {
+  if (!in || !wfrag || !bias || !out || B < 1 || H < 1 || W < 16 || W % 16 || ostride % 4 || ooff % 4 ||
+      !((cin == 32 && cout == 16) || (cin == 64 && cout == 32)))
+    return refused(c_err, what, " (W a multiple of 16; 32 -> 16 or 64 -> 32 channels)");
+  const long long ntiles = (long long)B * H * W / 16;
+  const dim3 grid((unsigned)((ntiles + 3) / 4)), blk(256);
+  if (cin == 32) hipLaunchKernelGGL((k_convt2x2<32, 16, X3>), grid, blk, 0, st, in, (const uint16_t*)wfrag, bias, out, H, W, ostride, ooff, ntiles);
+  else hipLaunchKernelGGL((k_convt2x2<64, 32, X3>), grid, blk, 0, st, in, (const uint16_t*)wfrag, bias, out, H, W, ostride, ooff, ntiles);
+  return launched(c_err, what);
+}
+
+// srl_conv3x3_relu_project (X3: _f32)
+template <bool X3>
+int relu_project(const char* what, const void* in, const void* wfrag, const float* bias, const float* proj_w, float proj_b, float* out,
+                 int B, int H, int W, int Hv, int Wv, hipStream_t st) {
+  if (!in || !wfrag || !bias || !proj_w || !out || B < 1 || H < 16 || W < 16 || H % 16 || W % 16 || Hv < 1 || Hv > H ||
+      Wv < 1 || Wv > W)
+    return refused(c_err, what, "");
+  const dim3 grid((W / 16) * (H / 16), B), blk(256);
+  if constexpr (X3)
+    hipLaunchKernelGGL((k_conv3x3_x3<16, 16, 1, true>), grid, blk, tile_lds<16>(true), st, (const float*)in, (const uint16_t*)wfrag, bias,
+                       (float*)nullptr, (float*)nullptr, H, W, 16, 0, 0, proj_w, proj_b, out, Hv, Wv);
   else
-    hipLaunchKernelGGL((k_thin_conv3x3_x3<2, float, PROJ>), grid, blk, lds, st, (const float*)in, w1, b1, wf, bias, out, pooled, H, W, ostride, ooff, nchw, pw, pb, proj_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(c_err, sizeof c_err, "%s: %s", what, hipGetErrorString(e)); return 2; }
-  return 0;
+    hipLaunchKernelGGL((k_conv3x3<16, 16, 1, true>), grid, blk, tile_lds<16>(false), st, (const uint16_t*)in, (const uint16_t*)wfrag, bias,
+                       (uint16_t*)nullptr, (uint16_t*)nullptr, H, W, 16, 0, 0, proj_w, proj_b, out, Hv, Wv);
+  return launched(c_err, what);
 }
 
 }  // namespace
@@ -783,23 +784,6 @@ int launch_thin_conv(const char* what, const void* in, int32_t in_dtype, int32_t
 extern "C" {
 
 const char* srl_conv_last_error(void) { return c_err; }
-
-int srl_conv3x3_bias_relu_f32(const float* in, const void* wfrag, const float* bias, float* out, float* pooled, int32_t B,
-                              int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t out_stride, int32_t out_offset,
-                              int32_t nchw, void* stream) {
-  if (!in || !wfrag || !bias || !out || B < 1 || H < 16 || W < 16 || H % 16 || W % 16 || out_stride % 4 || out_offset % 4 ||
-      srl_conv3x3_wfrag_elems(cin, cout) < 0 || (pooled && nchw)) {
-    snprintf(c_err, sizeof c_err, "srl_conv3x3_bias_relu_f32: bad arguments (H, W multiples of 16; cin in {16, 32, 64}, cout in {16, 32})");
-    return 1;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (cin == 16 && cout == 16) return launch_x3<16, 16>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  if (cin == 16 && cout == 32) return launch_x3<16, 32>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  if (cin == 32 && cout == 16) return launch_x3<32, 16>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  if (cin == 32 && cout == 32) return launch_x3<32, 32>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  if (cin == 64 && cout == 16) return launch_x3<64, 16>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  return launch_x3<64, 32>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-}
 
 int32_t srl_conv3x3_wfrag_elems(int32_t cin, int32_t cout) {
   if ((cin != 16 && cin != 32 && cin != 64) || (cout != 16 && cout != 32)) return -1;
@@ -809,18 +793,15 @@ int32_t srl_conv3x3_wfrag_elems(int32_t cin, int32_t cout) {
 int srl_conv3x3_bias_relu(const void* in, const void* wfrag, const float* bias, void* out, void* pooled, int32_t B,
                           int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t out_stride, int32_t out_offset,
                           int32_t nchw, void* stream) {
-  if (!in || !wfrag || !bias || !out || B < 1 || H < 16 || W < 16 || H % 16 || W % 16 || out_stride % 4 || out_offset % 4 ||
-      srl_conv3x3_wfrag_elems(cin, cout) < 0 || (pooled && nchw)) {
-    snprintf(c_err, sizeof c_err, "srl_conv3x3_bias_relu: bad arguments (H, W multiples of 16; cin in {16, 32, 64}, cout in {16, 32})");
-    return 1;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (cin == 16 && cout == 16) return launch<16, 16>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  if (cin == 16 && cout == 32) return launch<16, 32>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  if (cin == 32 && cout == 16) return launch<32, 16>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  if (cin == 32 && cout == 32) return launch<32, 32>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  if (cin == 64 && cout == 16) return launch<64, 16>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
-  return launch<64, 32>(in, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw, st);
+  return conv3x3<false>("srl_conv3x3_bias_relu", in, wfrag, bias, out, pooled, B, H, W, cin, cout, out_stride, out_offset, nchw,
+                        (hipStream_t)stream);
+}
+
+int srl_conv3x3_bias_relu_f32(const float* in, const void* wfrag, const float* bias, float* out, float* pooled, int32_t B,
+                              int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t out_stride, int32_t out_offset,
+                              int32_t nchw, void* stream) {
+  return conv3x3<true>("srl_conv3x3_bias_relu_f32", in, wfrag, bias, out, pooled, B, H, W, cin, cout, out_stride, out_offset, nchw,
+                       (hipStream_t)stream);
 }
 
 int srl_conv3x3_thin(const void* in, int32_t in_dtype, const float* w, const float* bias, void* out, int32_t B, int32_t H,
@@ -841,89 +822,40 @@ int32_t srl_convt2x2_wfrag_elems(int32_t cin, int32_t cout) {
 
 int srl_convt2x2_bias_relu(const void* in, const void* wfrag, const float* bias, void* out, int32_t B, int32_t H, int32_t W,
                            int32_t cin, int32_t cout, int32_t out_stride, int32_t out_offset, void* stream) {
-  if (!in || !wfrag || !bias || !out || B < 1 || H < 1 || W < 16 || W % 16 || out_stride % 4 || out_offset % 4 ||
-      !((cin == 32 && cout == 16) || (cin == 64 && cout == 32))) {
-    snprintf(c_err, sizeof c_err, "srl_convt2x2_bias_relu: bad arguments (W a multiple of 16; 32 -> 16 or 64 -> 32 channels)");
-    return 1;
-  }
-  const long long ntiles = (long long)B * H * W / 16;
-  const dim3 grid((unsigned)((ntiles + 3) / 4)), blk(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (cin == 32) hipLaunchKernelGGL((k_convt2x2<32, 16>), grid, blk, 0, st, (const uint16_t*)in, (const uint16_t*)wfrag, bias, (uint16_t*)out, H, W, out_stride, out_offset, ntiles);
-  else hipLaunchKernelGGL((k_convt2x2<64, 32>), grid, blk, 0, st, (const uint16_t*)in, (const uint16_t*)wfrag, bias, (uint16_t*)out, H, W, out_stride, out_offset, ntiles);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(c_err, sizeof c_err, "srl_convt2x2_bias_relu: %s", hipGetErrorString(e)); return 2; }
-  return 0;
+  return convt2x2<false>("srl_convt2x2_bias_relu", in, wfrag, bias, out, B, H, W, cin, cout, out_stride, out_offset, (hipStream_t)stream);
 }
 
 int srl_convt2x2_bias_relu_f32(const float* in, const void* wfrag, const float* bias, float* out, int32_t B, int32_t H, int32_t W,
                                int32_t cin, int32_t cout, int32_t out_stride, int32_t out_offset, void* stream) {
-  if (!in || !wfrag || !bias || !out || B < 1 || H < 1 || W < 16 || W % 16 || out_stride % 4 || out_offset % 4 ||
-      !((cin == 32 && cout == 16) || (cin == 64 && cout == 32))) {
-    snprintf(c_err, sizeof c_err, "srl_convt2x2_bias_relu_f32: bad arguments (W a multiple of 16; 32 -> 16 or 64 -> 32 channels)");
-    return 1;
-  }
-  const long long ntiles = (long long)B * H * W / 16;
-  const dim3 grid((unsigned)((ntiles + 3) / 4)), blk(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (cin == 32) hipLaunchKernelGGL((k_convt2x2_x3<32, 16>), grid, blk, 0, st, in, (const uint16_t*)wfrag, bias, out, H, W, out_stride, out_offset, ntiles);
-  else hipLaunchKernelGGL((k_convt2x2_x3<64, 32>), grid, blk, 0, st, in, (const uint16_t*)wfrag, bias, out, H, W, out_stride, out_offset, ntiles);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(c_err, sizeof c_err, "srl_convt2x2_bias_relu_f32: %s", hipGetErrorString(e)); return 2; }
-  return 0;
+  return convt2x2<true>("srl_convt2x2_bias_relu_f32", in, wfrag, bias, out, B, H, W, cin, cout, out_stride, out_offset, (hipStream_t)stream);
+}
+
+int srl_conv3x3_relu_project(const void* in, const void* wfrag, const float* bias, const float* proj_w, float proj_b,
+                             float* out, int32_t B, int32_t H, int32_t W, int32_t Hv, int32_t Wv, void* stream) {
+  return relu_project<false>("srl_conv3x3_relu_project", in, wfrag, bias, proj_w, proj_b, out, B, H, W, Hv, Wv, (hipStream_t)stream);
 }
 
 int srl_conv3x3_relu_project_f32(const float* in, const void* wfrag, const float* bias, const float* proj_w, float proj_b,
                                  float* out, int32_t B, int32_t H, int32_t W, int32_t Hv, int32_t Wv, void* stream) {
-  if (!in || !wfrag || !bias || !proj_w || !out || B < 1 || H < 16 || W < 16 || H % 16 || W % 16 || Hv < 1 || Hv > H ||
-      Wv < 1 || Wv > W) {
-    snprintf(c_err, sizeof c_err, "srl_conv3x3_relu_project_f32: bad arguments");
-    return 1;
-  }
-  const size_t lds = 2 * sizeof(uint16_t) * ConvCfg<16>::TW * ConvCfg<16>::TW * ConvCfg<16>::PS;
-  hipLaunchKernelGGL((k_conv3x3_x3<16, 16, 1, true>), dim3((W / 16) * (H / 16), B), dim3(256), lds, (hipStream_t)stream, in,
-                     (const uint16_t*)wfrag, bias, (float*)nullptr, (float*)nullptr, H, W, 16, 0, 0, proj_w, proj_b, out, Hv, Wv);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(c_err, sizeof c_err, "srl_conv3x3_relu_project_f32: %s", hipGetErrorString(e)); return 2; }
-  return 0;
+  return relu_project<true>("srl_conv3x3_relu_project_f32", in, wfrag, bias, proj_w, proj_b, out, B, H, W, Hv, Wv, (hipStream_t)stream);
 }
 
 int srl_thin_conv3x3_bias_relu_f32(const void* in, int32_t in_dtype, int32_t cin, const float* w1, const float* b1, const void* wfrag,
                                    const float* bias, float* out, float* pooled, int32_t B, int32_t H, int32_t W,
                                    int32_t out_stride, int32_t out_offset, int32_t nchw, void* stream) {
   if (!in || !w1 || !b1 || !wfrag || !bias || !out || B < 1 || H < 16 || W < 16 || H % 16 || W % 16 || out_stride % 4 ||
-      out_offset % 4 || (cin != 1 && cin != 2) || (in_dtype != 0 && in_dtype != 1) || (pooled && nchw)) {
-    snprintf(c_err, sizeof c_err, "srl_thin_conv3x3_bias_relu_f32: bad arguments (H, W multiples of 16; cin in {1, 2}; in_dtype 0 = uint8 / 255, 1 = float32)");
-    return 1;
-  }
+      out_offset % 4 || (cin != 1 && cin != 2) || (in_dtype != 0 && in_dtype != 1) || (pooled && nchw))
+    return refused(c_err, "srl_thin_conv3x3_bias_relu_f32", " (H, W multiples of 16; cin in {1, 2}; in_dtype 0 = uint8 / 255, 1 = float32)");
   return launch_thin_conv<false>("srl_thin_conv3x3_bias_relu_f32", in, in_dtype, cin, w1, b1, wfrag, bias, out, pooled, B, H, W,
                                  out_stride, out_offset, nchw, nullptr, 0.0f, nullptr, (hipStream_t)stream);
 }
 
 int srl_thin_conv3x3_relu_project_f32(const float* in, const float* w1, const float* b1, const void* wfrag, const float* bias,
                                       const float* proj_w, float proj_b, float* out, int32_t B, int32_t H, int32_t W, void* stream) {
-  if (!in || !w1 || !b1 || !wfrag || !bias || !proj_w || !out || B < 1 || H < 1 || W < 1) {
-    snprintf(c_err, sizeof c_err, "srl_thin_conv3x3_relu_project_f32: bad arguments");
-    return 1;
-  }
+  if (!in || !w1 || !b1 || !wfrag || !bias || !proj_w || !out || B < 1 || H < 1 || W < 1)
+    return refused(c_err, "srl_thin_conv3x3_relu_project_f32", "");
   return launch_thin_conv<true>("srl_thin_conv3x3_relu_project_f32", in, 1, 1, w1, b1, wfrag, bias, nullptr, nullptr, B, H, W, 16, 0, 0,
                                 proj_w, proj_b, out, (hipStream_t)stream);
-}
-
-int srl_conv3x3_relu_project(const void* in, const void* wfrag, const float* bias, const float* proj_w, float proj_b,
-                             float* out, int32_t B, int32_t H, int32_t W, int32_t Hv, int32_t Wv, void* stream) {
-  if (!in || !wfrag || !bias || !proj_w || !out || B < 1 || H < 16 || W < 16 || H % 16 || W % 16 || Hv < 1 || Hv > H ||
-      Wv < 1 || Wv > W) {
-    snprintf(c_err, sizeof c_err, "srl_conv3x3_relu_project: bad arguments");
-    return 1;
-  }
-  const size_t lds = sizeof(uint16_t) * ConvCfg<16>::TW * ConvCfg<16>::TW * ConvCfg<16>::PS;
-  hipLaunchKernelGGL((k_conv3x3<16, 16, 1, true>), dim3((W / 16) * (H / 16), B), dim3(256), lds, (hipStream_t)stream,
-                     (const uint16_t*)in, (const uint16_t*)wfrag, bias, (uint16_t*)nullptr, (uint16_t*)nullptr, H, W, 16, 0, 0,
-                     proj_w, proj_b, out, Hv, Wv);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(c_err, sizeof c_err, "srl_conv3x3_relu_project: %s", hipGetErrorString(e)); return 2; }
-  return 0;
 }
 
 }  // extern "C"

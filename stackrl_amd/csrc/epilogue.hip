@@ -12,12 +12,15 @@
 //
 // Reference ops replaced: Conv2D bias + activation='relu', MaxPool2D, Concatenate of `layers.unet`
 // (stackrl/nets/layers.py:135-259).  8 channels (16 bytes of bf16) per thread.
+// The bias gradient's pixels-per-block rule and finishing kernel are csrc/bias_grad.h (shared with csrc/train_conv.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/stackrl_qnet.h"
+#include "bias_grad.h"
 #include "srl_bf16.h"
+#include "srl_error.h"
 
 namespace {
 
@@ -141,8 +144,7 @@ __global__ void __launch_bounds__(256) k_pool2x2(const E* __restrict__ in, E* __
 // Backward of y = relu(x + bias) (or y = x + bias) for the update path (`DQN.train`, agents/dqn.py:466-469): the gradient
 // with respect to x, gx = gy * (y > 0), and the per-block partial sums of the bias gradient, one pass over gy and y.
 // float32 channels-last [npix][C]; a block walks `pixb` consecutive pixels, thread = (pixel lane, 8-channel group).
-// The partials are summed in index order by k_bias_grad_finish: a fixed summation order and no cross-block
-// synchronisation inside a kernel.
+// The partials are summed in index order by k_bias_grad_finish (csrc/bias_grad.h).
 __global__ void __launch_bounds__(256) k_bias_act_bwd(const float* __restrict__ gy, const float* __restrict__ y,
                                                       float* __restrict__ gx, float* __restrict__ partial, long long npix,
                                                       int C, int relu, int pixb) {
@@ -176,40 +178,31 @@ __global__ void __launch_bounds__(256) k_bias_act_bwd(const float* __restrict__ 
   }
 }
 
-// gb[c] = sum over blocks of partial[b][c], in a fixed order: a workgroup takes 32 channels (or all C < 32), its 256
-// threads are (row r, channel): row r adds the blocks r, r + rows, ... in turn (coalesced 128-byte reads), then the rows
-// are added in index order.
-__global__ void __launch_bounds__(256) k_bias_grad_finish(const float* __restrict__ partial, int nblk, int C,
-                                                          float* __restrict__ gb) {
-  __shared__ float sh[256];
-  const int cw = C < 32 ? C : 32, rows = 256 / cw;
-  const int c = blockIdx.x * cw + threadIdx.x % cw, r = threadIdx.x / cw;
-  float s = 0.0f;
-  if (r < rows && c < C)
-    for (int b = r; b < nblk; b += rows) s += partial[(long long)b * C + c];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x < cw && c < C) {
-    float t = 0.0f;
-    for (int q = 0; q < rows; ++q) t += sh[q * cw + threadIdx.x];
-    gb[c] = t;
-  }
-}
-
-// pixels per block of k_bias_act_bwd: at most 1,024 blocks, whole iterations of the block's pixel lanes
-static int bwd_pixb(long long npix, int C) {
-  const int ppi = 256 / (C / 8);
-  long long pixb = (npix + 1023) / 1024;
-  if (pixb < 4 * ppi) pixb = 4 * ppi;
-  return (int)((pixb + ppi - 1) / ppi * ppi);
-}
-
 thread_local char e_err[256] = "";
 
-int finish(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(e_err, sizeof e_err, "%s: %s", what, hipGetErrorString(e)); return 2; }
-  return 0;
+// srl_bias_act (E = bf16) and srl_bias_act_f32
+template <typename E>
+int bias_act(const char* what, const void* in, void* out, const float* bias, int64_t npix, int32_t C, int32_t out_stride,
+             int32_t out_offset, int32_t nchw_hw, int32_t relu, void* stream) {
+  if (!in || !out || !bias || npix < 1 || C < 8 || C % 8 || out_stride % 8 || out_offset % 8 || (nchw_hw > 0 && npix % nchw_hw))
+    return refused(e_err, what, " (channel counts, strides and offsets must be multiples of 8)");
+  const long long n = npix * (C / 8);
+  hipLaunchKernelGGL(k_bias_act<E>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const E*)in, (E*)out, bias,
+                     (long long)npix, C, out_stride, out_offset, nchw_hw, relu);
+  return launched(e_err, what);
+}
+
+// srl_bias_act_pool (E = bf16) and srl_bias_act_pool_f32
+template <typename E>
+int bias_act_pool(const char* what, const void* in, void* skip, void* pooled, const float* bias, int32_t B, int32_t H, int32_t W,
+                  int32_t C, int32_t skip_stride, int32_t skip_offset, void* stream) {
+  if (!in || !skip || !pooled || !bias || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 8 || C % 8 || skip_stride % 8 ||
+      skip_offset % 8)
+    return refused(e_err, what, "");
+  const long long n = (long long)B * (H / 2) * (W / 2) * (C / 8);
+  hipLaunchKernelGGL(k_bias_act_pool<E>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const E*)in, (E*)skip,
+                     (E*)pooled, bias, B, H, W, C, skip_stride, skip_offset);
+  return launched(e_err, what);
 }
 
 }  // namespace
@@ -220,87 +213,51 @@ const char* srl_epilogue_last_error(void) { return e_err; }
 
 int srl_bias_act(const void* in, void* out, const float* bias, int64_t npix, int32_t C, int32_t out_stride,
                  int32_t out_offset, int32_t nchw_hw, int32_t relu, void* stream) {
-  if (!in || !out || !bias || npix < 1 || C < 8 || C % 8 || out_stride % 8 || out_offset % 8 ||
-      (nchw_hw > 0 && npix % nchw_hw)) {
-    snprintf(e_err, sizeof e_err, "srl_bias_act: bad arguments (channel counts, strides and offsets must be multiples of 8)");
-    return 1;
-  }
-  const long long n = npix * (C / 8);
-  hipLaunchKernelGGL(k_bias_act<uint16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in,
-                     (uint16_t*)out, bias, (long long)npix, C, out_stride, out_offset, nchw_hw, relu);
-  return finish("srl_bias_act");
+  return bias_act<uint16_t>("srl_bias_act", in, out, bias, npix, C, out_stride, out_offset, nchw_hw, relu, stream);
 }
 
 int srl_bias_act_f32(const float* in, float* out, const float* bias, int64_t npix, int32_t C, int32_t out_stride,
                      int32_t out_offset, int32_t nchw_hw, int32_t relu, void* stream) {
-  if (!in || !out || !bias || npix < 1 || C < 8 || C % 8 || out_stride % 8 || out_offset % 8 ||
-      (nchw_hw > 0 && npix % nchw_hw)) {
-    snprintf(e_err, sizeof e_err, "srl_bias_act_f32: bad arguments (channel counts, strides and offsets must be multiples of 8)");
-    return 1;
-  }
-  const long long n = npix * (C / 8);
-  hipLaunchKernelGGL(k_bias_act<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out, bias,
-                     (long long)npix, C, out_stride, out_offset, nchw_hw, relu);
-  return finish("srl_bias_act_f32");
+  return bias_act<float>("srl_bias_act_f32", in, out, bias, npix, C, out_stride, out_offset, nchw_hw, relu, stream);
 }
 
 int srl_bias_act_pool(const void* in, void* skip, void* pooled, const float* bias, int32_t B, int32_t H, int32_t W,
                       int32_t C, int32_t skip_stride, int32_t skip_offset, void* stream) {
-  if (!in || !skip || !pooled || !bias || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 8 || C % 8 ||
-      skip_stride % 8 || skip_offset % 8) {
-    snprintf(e_err, sizeof e_err, "srl_bias_act_pool: bad arguments");
-    return 1;
-  }
-  const long long n = (long long)B * (H / 2) * (W / 2) * (C / 8);
-  hipLaunchKernelGGL(k_bias_act_pool<uint16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint16_t*)in, (uint16_t*)skip, (uint16_t*)pooled, bias, B, H, W, C, skip_stride, skip_offset);
-  return finish("srl_bias_act_pool");
+  return bias_act_pool<uint16_t>("srl_bias_act_pool", in, skip, pooled, bias, B, H, W, C, skip_stride, skip_offset, stream);
 }
 
 int srl_bias_act_pool_f32(const float* in, float* skip, float* pooled, const float* bias, int32_t B, int32_t H, int32_t W,
                           int32_t C, int32_t skip_stride, int32_t skip_offset, void* stream) {
-  if (!in || !skip || !pooled || !bias || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 8 || C % 8 ||
-      skip_stride % 8 || skip_offset % 8) {
-    snprintf(e_err, sizeof e_err, "srl_bias_act_pool_f32: bad arguments");
-    return 1;
-  }
-  const long long n = (long long)B * (H / 2) * (W / 2) * (C / 8);
-  hipLaunchKernelGGL(k_bias_act_pool<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, skip,
-                     pooled, bias, B, H, W, C, skip_stride, skip_offset);
-  return finish("srl_bias_act_pool_f32");
+  return bias_act_pool<float>("srl_bias_act_pool_f32", in, skip, pooled, bias, B, H, W, C, skip_stride, skip_offset, stream);
 }
 
 int64_t srl_bias_act_bwd_scratch_floats(int64_t npix, int32_t C) {
   if (npix < 1 || C < 8 || C % 8 || C > 256 || 256 % (C / 8)) return -1;
-  const int pixb = bwd_pixb(npix, C);
+  const int pixb = bias_grad_pixb(npix, C, 8);
   return ((npix + pixb - 1) / pixb) * C;
 }
 
 int srl_bias_act_bwd_f32(const float* gy, const float* y, float* gx, float* gbias, float* scratch, int64_t npix, int32_t C,
                          int32_t relu, void* stream) {
-  if (!gy || (relu && !y) || !gx || !gbias || !scratch || srl_bias_act_bwd_scratch_floats(npix, C) < 0) {
-    snprintf(e_err, sizeof e_err, "srl_bias_act_bwd_f32: bad arguments (C a multiple of 8 that divides 2,048, at most 256)");
-    return 1;
-  }
-  const int pixb = bwd_pixb(npix, C);
+  if (!gy || (relu && !y) || !gx || !gbias || !scratch || srl_bias_act_bwd_scratch_floats(npix, C) < 0)
+    return refused(e_err, "srl_bias_act_bwd_f32", " (C a multiple of 8 that divides 2,048, at most 256)");
+  const int pixb = bias_grad_pixb(npix, C, 8);
   const int nblk = (int)((npix + pixb - 1) / pixb);
   hipLaunchKernelGGL(k_bias_act_bwd, dim3(nblk), dim3(256), 0, (hipStream_t)stream, gy, y, gx, scratch, (long long)npix, C,
                      relu, pixb);
   hipLaunchKernelGGL(k_bias_grad_finish, dim3((C + 31) / 32), dim3(256), 0, (hipStream_t)stream, scratch, nblk, C, gbias);
-  return finish("srl_bias_act_bwd_f32");
+  return launched(e_err, "srl_bias_act_bwd_f32");
 }
 
 int srl_pool2x2(const void* in, void* pooled, int32_t B, int32_t H, int32_t W, int32_t C, int32_t in_stride, int32_t in_offset,
                 int32_t f32, void* stream) {
-  if (!in || !pooled || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 8 || C % 8 || in_stride % 8 || in_offset % 8) {
-    snprintf(e_err, sizeof e_err, "srl_pool2x2: bad arguments");
-    return 1;
-  }
+  if (!in || !pooled || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 8 || C % 8 || in_stride % 8 || in_offset % 8)
+    return refused(e_err, "srl_pool2x2", "");
   const long long n = (long long)B * (H / 2) * (W / 2) * (C / 8);
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
   if (f32) hipLaunchKernelGGL(k_pool2x2<float>, grid, blk, 0, (hipStream_t)stream, (const float*)in, (float*)pooled, B, H, W, C, in_stride, in_offset);
   else hipLaunchKernelGGL(k_pool2x2<uint16_t>, grid, blk, 0, (hipStream_t)stream, (const uint16_t*)in, (uint16_t*)pooled, B, H, W, C, in_stride, in_offset);
-  return finish("srl_pool2x2");
+  return launched(e_err, "srl_pool2x2");
 }
 
 }  // extern "C"

@@ -16,7 +16,8 @@
 //                       every workgroup reduces its pixel tiles in a fixed order and writes ONE partial, a second kernel
 //                       adds the partials in index order (no atomics, no zero-fill, bit-identical on repetition).
 //   k_tact_bwd          gz = (g [+ the gradient routed back through the 2 x 2 max-pool]) * [y > 0], the bias gradient
-//                       as fixed-order partial sums; optionally stored space-to-depth (for the transposed convolutions).
+//                       as fixed-order partial sums (finished by csrc/bias_grad.h's kernel, shared with csrc/epilogue.hip);
+//                       optionally stored space-to-depth (for the transposed convolutions).
 //   k_trepack           all packed weight layouts of all layers from the flat parameter bucket in ONE launch.
 //
 // Operand layouts are chosen so that no transposition is needed: with D[m][n] += A[m][k] B[k][n] and lane l holding
@@ -32,18 +33,14 @@
 #include <stdio.h>
 
 #include "../../include/stackrl_qnet.h"
+#include "bias_grad.h"
+#include "srl_error.h"
 
 namespace {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 thread_local char t_err[256] = "";
-
-int t_finish(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(t_err, sizeof t_err, "%s: %s", what, hipGetErrorString(e)); return 2; }
-  return 0;
-}
 
 int t_bad(const char* msg) { snprintf(t_err, sizeof t_err, "%s", msg); return 1; }
 
@@ -368,7 +365,7 @@ __global__ void __launch_bounds__(256) k_twrw_finish(const float* __restrict__ p
 // gz[p][c] = (g[p][c] + routed pool gradient) * [y[p][c] > 0]; thread = (pixel, 4-channel group).  gp (may be NULL):
 // gradient of the 2 x 2 max-pooled map [B][H/2][W/2][C]: it goes to the first maximal element of the window in row-major
 // order (the library's rule).  s2d: gz is stored space-to-depth, [B][H/2][W/2][4 C] with channel q C + c, q = 2 (y % 2) +
-// x % 2.  Bias-gradient partials per block (fixed order), finished by k_tbias_finish.
+// x % 2.  Bias-gradient partials per block (fixed order), finished by k_bias_grad_finish (csrc/bias_grad.h).
 __global__ void __launch_bounds__(256) k_tact_bwd(const float* __restrict__ g, int gs, int go, const float* __restrict__ y,
                                                   int ys, int yo, const float* __restrict__ gp, float* __restrict__ gz,
                                                   float* __restrict__ partial, int B, int H, int W, int C, int relu,
@@ -423,29 +420,6 @@ __global__ void __launch_bounds__(256) k_tact_bwd(const float* __restrict__ g, i
   }
 }
 
-__global__ void __launch_bounds__(256) k_tbias_finish(const float* __restrict__ partial, int nblk, int C, float* __restrict__ gb) {
-  __shared__ float sh[256];
-  const int cw = C < 32 ? C : 32, rows = 256 / cw;
-  const int c = blockIdx.x * cw + threadIdx.x % cw, r = threadIdx.x / cw;
-  float s = 0.0f;
-  if (r < rows && c < C)
-    for (int b = r; b < nblk; b += rows) s += partial[(long long)b * C + c];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x < cw && c < C) {
-    float t = 0.0f;
-    for (int q = 0; q < rows; ++q) t += sh[q * cw + threadIdx.x];
-    gb[c] = t;
-  }
-}
-
-int act_pixb(long long npix, int C) {
-  const int ppi = 256 / (C / 4);
-  long long pixb = (npix + 1023) / 1024;
-  if (pixb < 4 * ppi) pixb = 4 * ppi;
-  return (int)((pixb + ppi - 1) / ppi * ppi);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- repack
 // desc[i] = {src_off, dst_off, cin, cout, taps, kind, cin_pad (kind 1; 0 = cin), 0} (int64 x 8); one thread per destination element.
 //   kind 0  conv forward     dst[(t cin_p + ci) cout + co]       = w[co][ci][t]            (ci >= cin: 0), cin_p = cin up to 4
@@ -495,7 +469,7 @@ int launch_conv(const float* x, int xs, int xo, const float* wp, const float* bi
     hipLaunchKernelGGL((k_tconv<TAPS, TW, 2>), dim3((unsigned)tiles, cout / 32), dim3(256), 0, st, x, xs, xo, wp, bias, y, ys, yo, B, H, W, cin, cout, relu, d2s);
   else
     hipLaunchKernelGGL((k_tconv<TAPS, TW, 1>), dim3((unsigned)tiles, cout / 16), dim3(256), 0, st, x, xs, xo, wp, bias, y, ys, yo, B, H, W, cin, cout, relu, d2s);
-  return t_finish("srl_tconv");
+  return launched(t_err, "srl_tconv");
 }
 
 long long wrw_tiles(int taps, int B, int H, int W) {
@@ -527,7 +501,7 @@ int launch_wrw(const float* x, int xs, int xo, const float* gz, float* partial, 
     hipLaunchKernelGGL((k_twrw<TAPS, TW, 2>), dim3(G, nci, cout / 32), dim3(256), 0, st, x, xs, xo, gz, partial, B, H, W, cin, cout, tiles);
   else
     hipLaunchKernelGGL((k_twrw<TAPS, TW, 1>), dim3(G, nci, cout / 16), dim3(256), 0, st, x, xs, xo, gz, partial, B, H, W, cin, cout, tiles);
-  return t_finish("srl_twrw");
+  return launched(t_err, "srl_twrw");
 }
 
 
@@ -810,18 +784,18 @@ int srl_twrw(const float* x, int32_t x_stride, int32_t x_off, const float* gz, f
   const int nwb = (int)((n + 31) / 32), nbb = (bias_partial && gbias) ? (bias_C + 31) / 32 : 0;
   hipLaunchKernelGGL(k_twrw_finish, dim3(nwb + nbb), dim3(256), 0, st, scratch, G, taps, cin, cout, convt ? 1 : 0, gw, nwb,
                      bias_partial, bias_nblk, bias_C, gbias);
-  return t_finish("srl_twrw finish");
+  return launched(t_err, "srl_twrw finish");
 }
 
 int64_t srl_tact_bwd_scratch_floats(int64_t npix, int32_t C) {
   if (npix < 1 || C < 4 || C % 4 || C > 256 || 256 % (C / 4)) return -1;
-  const int pixb = act_pixb(npix, C);
+  const int pixb = bias_grad_pixb(npix, C, 4);
   return ((npix + pixb - 1) / pixb) * C;
 }
 
 int32_t srl_tact_bwd_blocks(int64_t npix, int32_t C) {
   if (srl_tact_bwd_scratch_floats(npix, C) < 0) return -1;
-  const int pixb = act_pixb(npix, C);
+  const int pixb = bias_grad_pixb(npix, C, 4);
   return (int32_t)((npix + pixb - 1) / pixb);
 }
 
@@ -832,26 +806,26 @@ int srl_tact_bwd(const float* g, int32_t g_stride, int32_t g_off, const float* y
   if (!g || !gz || (!y && (relu || gpool)) || srl_tact_bwd_scratch_floats(npix, C) < 0 || g_stride % 4 || g_off % 4 ||
       y_stride % 4 || y_off % 4 || ((gpool || s2d) && ((H | W) & 1)))
     return t_bad("srl_tact_bwd: bad arguments (C a multiple of 4 with C / 4 dividing 256, strides / offsets multiples of 4)");
-  const int pixb = act_pixb(npix, C);
+  const int pixb = bias_grad_pixb(npix, C, 4);
   const int nblk = (int)((npix + pixb - 1) / pixb);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_tact_bwd, dim3(nblk), dim3(256), 0, st, g, g_stride, g_off, y, y_stride, y_off, gpool, gz,
                      scratch, B, H, W, C, relu, s2d, pixb);
-  if (gbias) hipLaunchKernelGGL(k_tbias_finish, dim3((C + 31) / 32), dim3(256), 0, st, scratch, nblk, C, gbias);
-  return t_finish("srl_tact_bwd");
+  if (gbias) hipLaunchKernelGGL(k_bias_grad_finish, dim3((C + 31) / 32), dim3(256), 0, st, scratch, nblk, C, gbias);
+  return launched(t_err, "srl_tact_bwd");
 }
 
 int srl_trepack(const float* flat, float* packed, const int64_t* desc_dev, int32_t nlayers, int64_t total, void* stream) {
   if (!flat || !packed || !desc_dev || nlayers < 1 || total < 1) return t_bad("srl_trepack: bad arguments");
   hipLaunchKernelGGL(k_trepack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flat, packed,
                      (const long long*)desc_dev, nlayers, (long long)total);
-  return t_finish("srl_trepack");
+  return launched(t_err, "srl_trepack");
 }
 
 int srl_thead_fwd(const float* z, const float* pw, const float* pb, const float* v, float* q, int32_t B, int32_t A, void* stream) {
   if (!z || !pw || !pb || !v || !q || B < 1 || A < 1) return t_bad("srl_thead_fwd: bad arguments");
   hipLaunchKernelGGL(k_thead_fwd, dim3(B), dim3(256), 0, (hipStream_t)stream, z, pw, pb, v, q, A);
-  return t_finish("srl_thead_fwd");
+  return launched(t_err, "srl_thead_fwd");
 }
 
 int srl_thead_bwd(const float* z, const float* pw, const float* gq, float* gz, float* gv, float* gpw, float* gpb,
@@ -860,14 +834,14 @@ int srl_thead_bwd(const float* z, const float* pw, const float* gq, float* gz, f
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_thead_bwd, dim3(n), dim3(256), 0, st, z, pw, gq, gz, gv, scratch, A);
   hipLaunchKernelGGL(k_thead_finish, dim3(1), dim3(64), 0, st, scratch, n, gpw, gpb);
-  return t_finish("srl_thead_bwd");
+  return launched(t_err, "srl_thead_bwd");
 }
 
 int srl_tvalue_fwd(const float* x0, const float* W1, const float* b1, const float* W2, const float* b2, float* pooled, float* h,
                    float* v, int32_t B, int32_t P, int32_t C, int32_t U, void* stream) {
   if (!x0 || !W1 || !b1 || !W2 || !b2 || !v || B < 1 || P < 1 || C < 1 || U < 1 || C > 4096) return t_bad("srl_tvalue_fwd: bad arguments");
   hipLaunchKernelGGL(k_tvalue_fwd, dim3(B), dim3(256), sizeof(float) * (C + 256), (hipStream_t)stream, x0, W1, b1, W2, b2, pooled, h, v, P, C, U);
-  return t_finish("srl_tvalue_fwd");
+  return launched(t_err, "srl_tvalue_fwd");
 }
 
 int srl_tvalue_bwd(const float* gv, const float* h, const float* pooled, const float* W1, const float* W2, const float* gin,
@@ -879,7 +853,7 @@ int srl_tvalue_bwd(const float* gv, const float* h, const float* pooled, const f
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_tvalue_bwd_a, dim3(n), dim3(256), sizeof(float) * U, st, gv, h, W1, W2, gin, scratch, gx, P, C, U);
   hipLaunchKernelGGL(k_tvalue_bwd_b, dim3(U + 1), dim3(256), 0, st, gv, (const float*)scratch, h, pooled, gW1, gb1, gW2, gb2, n, C, U);
-  return t_finish("srl_tvalue_bwd");
+  return launched(t_err, "srl_tvalue_bwd");
 }
 
 int srl_tlayout(const float* src, int32_t src_stride, int32_t src_off, float* dst, int32_t B, int32_t HW, int32_t C, int32_t to_nhwc,
@@ -888,26 +862,26 @@ int srl_tlayout(const float* src, int32_t src_stride, int32_t src_off, float* ds
   const long long n = (long long)B * HW * C;
   hipLaunchKernelGGL(k_tlayout, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, src_stride, src_off, dst, B, HW, C,
                      to_nhwc ? 1 : 0);
-  return t_finish("srl_tlayout");
+  return launched(t_err, "srl_tlayout");
 }
 
 int srl_tcorr_grad(const float* g, int32_t g_stride, float* plain, float* padded, int32_t n, int32_t O, int32_t pad, void* stream) {
   if (!g || !plain || !padded || n < 1 || O < 1 || pad < 0 || g_stride < 1) return t_bad("srl_tcorr_grad: bad arguments");
   const long long tot = (long long)n * (O + 2 * pad) * (O + 2 * pad);
   hipLaunchKernelGGL(k_tcorr_grad, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, g_stride, plain, padded, n, O, pad);
-  return t_finish("srl_tcorr_grad");
+  return launched(t_err, "srl_tcorr_grad");
 }
 
 int srl_tflip(const float* in, float* out, int64_t planes, int32_t hw, void* stream) {
   if (!in || !out || planes < 1 || hw < 1) return t_bad("srl_tflip: bad arguments");
   hipLaunchKernelGGL(k_tflip, dim3((unsigned)((planes * hw + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out, (long long)planes, hw);
-  return t_finish("srl_tflip");
+  return launched(t_err, "srl_tflip");
 }
 
 int srl_tu8_to_f32(const uint8_t* in, float* out, int64_t n, void* stream) {
   if (!in || !out || n < 4 || n % 4) return t_bad("srl_tu8_to_f32: bad arguments (element count a multiple of 4)");
   hipLaunchKernelGGL(k_tu8_to_f32, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out, (long long)(n / 4));
-  return t_finish("srl_tu8_to_f32");
+  return launched(t_err, "srl_tu8_to_f32");
 }
 
 }  // extern "C"

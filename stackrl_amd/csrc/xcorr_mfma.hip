@@ -38,13 +38,11 @@
 
 #include "../../include/stackrl_greedy.h"
 #include "../../include/stackrl_qnet.h"
-#include "srl_bf16.h"
+#include "mfma_bf16.h"   // bf16x8, f32x4
 
 namespace {
 
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int HIN, int KH>
 struct XcorrCfg {

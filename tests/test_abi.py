@@ -109,6 +109,94 @@ def test_qnet_error_accessors_match_the_sources():
     assert err == (own[where[name]][0] if launches[name] else None), name
 
 
+_P = 64      # a non-null pointer: a refusal comes before anything is read through it
+_CONV3X3 = ': bad arguments (H, W multiples of 16; cin in {16, 32, 64}, cout in {16, 32})'
+_THIN = ': bad arguments (cin in {1, 2}; in_dtype 0 = uint8 / 255, 1 = float32)'
+_THIN_CONV = ': bad arguments (H, W multiples of 16; cin in {1, 2}; in_dtype 0 = uint8 / 255, 1 = float32)'
+_CONVT = ': bad arguments (W a multiple of 16; 32 -> 16 or 64 -> 32 channels)'
+_GEMM = ': bad arguments (layers: srl_conv3x3_gemm_supported; the batch a multiple of srl_conv3x3_gemm_batch_multiple)'
+_CONVT_GEMM = ': bad arguments (128 -> 64 or 256 -> 128 channels)'
+_BIAS_ACT = ': bad arguments (channel counts, strides and offsets must be multiples of 8)'
+_BIAS_BWD = ': bad arguments (C a multiple of 8 that divides 2,048, at most 256)'
+_PLAIN = ': bad arguments'
+# (export, arguments without the stream, the text after the export's name): one refused call per export of conv_mfma.hip,
+# conv_gemm.hip and epilogue.hip that launches, and one per clause of a check that a bf16 / _f32 pair shares
+_REFUSED = [
+  # in, wfrag, bias, out, pooled, B, H, W, cin, cout, out_stride, out_offset, nchw
+  ('srl_conv3x3_bias_relu', (None, _P, _P, _P, None, 2, 16, 16, 16, 16, 16, 0, 0), _CONV3X3),
+  ('srl_conv3x3_bias_relu', (_P, _P, _P, _P, None, 2, 17, 16, 16, 16, 16, 0, 0), _CONV3X3),
+  ('srl_conv3x3_bias_relu', (_P, _P, _P, _P, None, 2, 16, 16, 48, 16, 16, 0, 0), _CONV3X3),
+  ('srl_conv3x3_bias_relu', (_P, _P, _P, _P, None, 2, 16, 16, 16, 16, 16, 2, 0), _CONV3X3),
+  ('srl_conv3x3_bias_relu', (_P, _P, _P, _P, _P, 2, 16, 16, 16, 16, 16, 0, 1), _CONV3X3),
+  ('srl_conv3x3_bias_relu_f32', (_P, _P, _P, _P, None, 2, 17, 16, 16, 16, 16, 0, 0), _CONV3X3),
+  ('srl_conv3x3_bias_relu_f32', (_P, _P, _P, _P, _P, 2, 16, 16, 64, 32, 32, 0, 1), _CONV3X3),
+  # in, in_dtype, w, bias, out, B, H, W, cin, Hp, Wp
+  ('srl_conv3x3_thin', (_P, 0, _P, _P, _P, 2, 16, 16, 3, 16, 16), _THIN),
+  ('srl_conv3x3_thin', (_P, 2, _P, _P, _P, 2, 16, 16, 1, 16, 16), _THIN),
+  ('srl_conv3x3_thin', (_P, 0, _P, _P, _P, 2, 16, 16, 1, 15, 16), _THIN),
+  ('srl_conv3x3_thin_f32', (_P, 1, _P, _P, None, 2, 16, 16, 2, 16, 16), _THIN),
+  # in, wfrag, bias, proj_w, proj_b, out, B, H, W, Hv, Wv
+  ('srl_conv3x3_relu_project', (_P, _P, _P, _P, 0.5, _P, 2, 17, 16, 16, 16), _PLAIN),
+  ('srl_conv3x3_relu_project', (_P, _P, _P, _P, 0.5, _P, 2, 16, 16, 17, 16), _PLAIN),
+  ('srl_conv3x3_relu_project', (_P, _P, _P, None, 0.5, _P, 2, 16, 16, 16, 16), _PLAIN),
+  ('srl_conv3x3_relu_project_f32', (_P, _P, _P, _P, 0.5, _P, 2, 32, 32, 20, 0), _PLAIN),
+  # in, in_dtype, cin, w1, b1, wfrag, bias, out, pooled, B, H, W, out_stride, out_offset, nchw
+  ('srl_thin_conv3x3_bias_relu_f32', (_P, 0, 3, _P, _P, _P, _P, _P, None, 2, 16, 16, 16, 0, 0), _THIN_CONV),
+  ('srl_thin_conv3x3_bias_relu_f32', (_P, 0, 1, _P, _P, _P, _P, _P, _P, 2, 16, 16, 16, 0, 1), _THIN_CONV),
+  # in, w1, b1, wfrag, bias, proj_w, proj_b, out, B, H, W
+  ('srl_thin_conv3x3_relu_project_f32', (_P, _P, None, _P, _P, _P, 0.5, _P, 2, 20, 20), _PLAIN),
+  ('srl_thin_conv3x3_relu_project_f32', (_P, _P, _P, _P, _P, _P, 0.5, _P, 2, 0, 20), _PLAIN),
+  # in, wfrag, bias, out, B, H, W, cin, cout, out_stride, out_offset
+  ('srl_convt2x2_bias_relu', (_P, _P, _P, _P, 2, 8, 24, 32, 16, 32, 0), _CONVT),
+  ('srl_convt2x2_bias_relu', (_P, _P, _P, _P, 2, 8, 16, 32, 32, 32, 0), _CONVT),
+  ('srl_convt2x2_bias_relu', (_P, _P, _P, _P, 2, 8, 16, 32, 16, 32, 2), _CONVT),
+  ('srl_convt2x2_bias_relu_f32', (_P, _P, _P, _P, 2, 8, 16, 128, 64, 128, 0), _CONVT),
+  # in, wfrag, bias, out, B, W, cin, cout, out_stride, out_offset, f32
+  ('srl_conv3x3_gemm_bias_relu', (_P, _P, _P, _P, 2, 32, 16, 64, 64, 0, 0), _GEMM),
+  ('srl_conv3x3_gemm_bias_relu', (_P, _P, _P, _P, 3, 8, 128, 256, 256, 0, 1), _GEMM),
+  ('srl_conv3x3_gemm_bias_relu', (_P, None, _P, _P, 2, 32, 32, 64, 64, 0, 1), _GEMM),
+  # in, wfrag, bias, out, B, H, W, cin, cout, out_stride, out_offset, f32
+  ('srl_convt2x2_gemm_bias_relu', (_P, _P, _P, _P, 2, 8, 8, 64, 32, 64, 0, 0), _CONVT_GEMM),
+  ('srl_convt2x2_gemm_bias_relu', (_P, _P, _P, _P, 2, 8, 8, 128, 64, 128, 2, 1), _CONVT_GEMM),
+  # in, out, bias, npix, C, out_stride, out_offset, nchw_hw, relu
+  ('srl_bias_act', (_P, _P, _P, 10, 12, 16, 0, 0, 1), _BIAS_ACT),
+  ('srl_bias_act', (_P, _P, _P, 10, 16, 16, 2, 0, 1), _BIAS_ACT),
+  ('srl_bias_act', (_P, _P, _P, 10, 16, 16, 0, 3, 1), _BIAS_ACT),
+  ('srl_bias_act_f32', (_P, _P, None, 10, 16, 16, 0, 0, 1), _BIAS_ACT),
+  # in, skip, pooled, bias, B, H, W, C, skip_stride, skip_offset
+  ('srl_bias_act_pool', (_P, _P, _P, _P, 2, 3, 4, 16, 16, 0), _PLAIN),
+  ('srl_bias_act_pool', (_P, _P, _P, _P, 2, 4, 4, 12, 16, 0), _PLAIN),
+  ('srl_bias_act_pool', (_P, _P, _P, _P, 2, 4, 4, 16, 20, 0), _PLAIN),
+  ('srl_bias_act_pool_f32', (_P, _P, None, _P, 2, 4, 4, 16, 16, 0), _PLAIN),
+  # gy, y, gx, gbias, scratch, npix, C, relu
+  ('srl_bias_act_bwd_f32', (_P, _P, _P, _P, _P, 10, 12, 1), _BIAS_BWD),
+  ('srl_bias_act_bwd_f32', (_P, None, _P, _P, _P, 10, 16, 1), _BIAS_BWD),
+  # in, pooled, B, H, W, C, in_stride, in_offset, f32
+  ('srl_pool2x2', (_P, _P, 2, 3, 4, 16, 16, 0, 0), _PLAIN),
+  ('srl_pool2x2', (_P, _P, 2, 4, 4, 16, 16, 4, 1), _PLAIN),
+]
+
+
+def test_rollout_conv_exports_refuse_bad_arguments_with_their_own_text():
+  """Every launching export of conv_mfma.hip, conv_gemm.hip and epilogue.hip returns 1 for arguments it refuses (before any
+  HIP call: no GPU needed) and leaves "<its own name>: bad arguments..." behind its file's accessor."""
+  from stackrl_amd import build, qops
+  build.build()
+  L = ctypes.CDLL(build.QLIB)
+  files = {qops._CONV: 'conv_mfma.hip', qops._GEMM: 'conv_gemm.hip', qops._EPI: 'epilogue.hip'}
+  launching = {n for n, (res, _, err) in qops._SIGS.items() if err in files}
+  assert {n for n, _, _ in _REFUSED} == launching and len(launching) == 18
+  for name, args, tail in _REFUSED:
+    res, argtypes, err = qops._SIGS[name]
+    f = getattr(L, name)
+    f.restype, f.argtypes = res, argtypes
+    last = getattr(L, err)
+    last.restype, last.argtypes = ctypes.c_char_p, []
+    assert len(args) + 1 == len(argtypes), name
+    assert f(*args, None) == 1, (name, args)
+    assert last().decode() == name + tail, (name, args)
+
+
 def test_config_struct_matches_header():
   from stackrl_amd.config import CConfig, StackConfig
   with open(os.path.join(ROOT, 'include', 'srl_types.h')) as f:

@@ -217,7 +217,7 @@ def _activation_gradient_case(C, B, H, W, form):
   """gz = (g + pool gradient to the first maximum of each 2 x 2 window) * [y > 0] against autograd of
   relu -> (identity, max_pool2d); y holds ties (zeros after the ReLU and equal positive values).  form 'pool' as said,
   'plain' without the pooled branch, 's2d' without it and stored space-to-depth (the transposed convolution's backward).
-  The bias gradient is finished both ways: by `k_tbias_finish`, and deferred into `srl_twrw`'s finishing launch as `HandNet`
+  The bias gradient is finished both ways: by `k_bias_grad_finish`, and deferred into `srl_twrw`'s finishing launch as `HandNet`
   does (every partial the finishing launch adds comes from the poisoned scratch of `k_tact_bwd`)."""
   from stackrl_amd import qtrain
   F = torch.nn.functional

@@ -3,7 +3,7 @@
 The host code of csrc/train_conv.hip and csrc/xcorr_mfma.hip picks template instantiations and loop structures from the
 BATCH SIZE: how many output-channel tiles a `k_tconv` workgroup takes (`launch_conv`), how many pixel tiles a `k_twrw` group
 reduces and whether trailing groups are left without one (`wrw_groups`), how many pixels a `k_tact_bwd` block takes
-(`act_pixb`), how many channels a `k_xcorr_mfma` workgroup loops over (`channel_split`).  Each function below names the
+(`bias_grad_pixb`), how many channels a `k_xcorr_mfma` workgroup loops over (`channel_split`).  Each function below names the
 REGIME of one launch — the tuple of those choices — so that a test can say which regimes the product's update reaches
 (`product_regimes`) and which ones a list of test cases reaches.  tests/test_update_dispatch.py holds the restatement to the
 library wherever the library exports the quantity, and the GPU suite's parameter lists to the product's regimes."""
