@@ -605,6 +605,8 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
     if constexpr (VA::PAIR_SPLIT) sp = make_pair_split(L, tid);
     STAMP(5);
     const bool solo = VA::SOLO && misc[M_SOLO] != 0;
+    // the ground points' friction coefficient, made here once and kept as a scalar (not loaded and multiplied in every sweep)
+    const float gmu = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ground_mu(P.c))));
     const int gslot = gp.valid ? gp.idx : -1;
     // the lanes of the first two colours (solo sweeps: solver_sweep)
     unsigned long long cm[2], cm2[2] = {0ull, 0ull};
@@ -636,20 +638,20 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
           if (gb.np > 0) {
             vw_load(gb.pvw, v, w);
             float res = 0.0f;
-            ground_body<true, false, true>(gb, P.c.warmstart, v, w, res);
+            ground_body<true, false, true>(gb, P.c.warmstart, gmu, v, w, res);
           }
           for (int it = 0; it < P.c.solver_iterations; ++it) {
             done++;
             float res = 0.0f;
-            if (gb.np > 0) ground_body<false, GA, true>(gb, P.c.warmstart, v, w, res);
+            if (gb.np > 0) ground_body<false, GA, true>(gb, P.c.warmstart, gmu, v, w, res);
             if (__ballot(res * res > P.c.residual_threshold) == 0ull) break;
           }
           if (gb.np > 0) vw_store(gb.pvw, v, w);
         } else {
-          solver_sweep<true, T, PP, VA::SOLO>(L, gp, gb, pp, sp, ncol, gslot, pslot, 0, cm, cm2);
+          solver_sweep<true, T, PP, VA::SOLO>(L, gp, gb, pp, sp, ncol, gslot, pslot, 0, cm, cm2, gmu);
           for (int it = 0; it < P.c.solver_iterations; ++it) {
             done++;
-            if (!solver_sweep<false, T, PP, VA::SOLO>(L, gp, gb, pp, sp, ncol, gslot, pslot, 0, cm, cm2)) break;
+            if (!solver_sweep<false, T, PP, VA::SOLO>(L, gp, gb, pp, sp, ncol, gslot, pslot, 0, cm, cm2, gmu)) break;
           }
         }
         if (tid == 0) misc[M_CNT] = done;   // (M_CNT is free between the calls of newest_contacts)
@@ -657,10 +659,10 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
       __syncthreads();
       gsweep += misc[M_CNT];
     } else {
-      solver_sweep<true, T, PP, false>(L, gp, gb, pp, sp, ncol, gslot, pslot, 0, cm, cm2);
+      solver_sweep<true, T, PP, false>(L, gp, gb, pp, sp, ncol, gslot, pslot, 0, cm, cm2, gmu);
       for (int it = 0; it < P.c.solver_iterations; ++it) {
         gsweep++;
-        if (!solver_sweep<false, T, PP, false>(L, gp, gb, pp, sp, ncol, gslot, pslot, gsweep, cm, cm2)) break;
+        if (!solver_sweep<false, T, PP, false>(L, gp, gb, pp, sp, ncol, gslot, pslot, gsweep, cm, cm2, gmu)) break;
       }
     }
 #ifdef SRL_STAMPS

@@ -55,6 +55,9 @@ __device__ __forceinline__ void prow_apply(const PRow& r, Vel2& u, float imp) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) { u.a[c] = fma2(r.ua[c], d2, u.a[c]); u.b[c] = fma2(r.ub[c], d2, u.b[c]); }
 }
+// FRICTION: the row's target is 0 and r.rk holds -1 / k (make_pair_point): dl is the plain product vrel (-rk), which is
+// fma(-vrel, rk, 0 rk) but for the sign of a zero that acc + dl does not see (the argument: GRow below)
+template <bool FRICTION>
 __device__ __forceinline__ void prow_solve(const PRow& r, Vel2& u, float target, float& acc, float lo, float hi, float& res) {
   const f2 sa = fma2(r.ka[0], u.a[0], fma2(r.ka[1], u.a[1], r.ka[2] * u.a[2]));   // (dot(d, va), dot(ca, wa))
   const f2 sb = fma2(r.kb[0], u.b[0], fma2(r.kb[1], u.b[1], r.kb[2] * u.b[2]));   // (dot(d, vb), dot(cb, wb))
@@ -63,7 +66,7 @@ __device__ __forceinline__ void prow_solve(const PRow& r, Vel2& u, float target,
   const float vrel = ra - (sb.x + sb.y);
   // (target - vrel) rk as one fused step and the linear impulses as (d m^-1) dl: the products that do not depend on the
   // velocities leave the dependency chain (10 dependent operations per row instead of 12; the oracle evaluates the same)
-  float dl = fmaf(-vrel, r.rk, target * r.rk);
+  float dl = FRICTION ? vrel * r.rk : fmaf(-vrel, r.rk, target * r.rk);
   // the accumulated impulse clamped to [lo, hi] as the median of the three (v_med3_f32; the oracle restates its zero
   // handling): one instruction on the solver's dependency chain instead of two compare / select pairs through VCC,
   // each of which costs a lone wave its wait states — 6.68 -> 6.02 ms per launch at the headline shape
@@ -95,18 +98,48 @@ struct Point {
 // Ground rows.  The ground's normal is +z and its tangents (plane_space of +z) are -y and +x: a ground row's direction is
 // sgn e_axis, so its relative velocity takes one component of the linear velocity and its impulse changes that component
 // only (stated so in the oracle too): 13 instead of 25 operations per row, and 8 instead of 17 registers of row constants.
-struct GRow { v3 ca, aa; float rk, k; };
+//
+// The rows' structural zeros.  ca = ra x d is perpendicular to d = sgn e_axis, so its component `axis` is an exact zero in every
+// ground row, and the other six components of a point's three rows are four values:
+//   normal    (+z)  ca = ( ra.y, -ra.x,   ±0 )
+//   tangent 1 (-y)  ca = ( ra.z,   ±0, -ra.x )
+//   tangent 2 (+x)  ca = (  ±0,  ra.z, -ra.y )
+// (cross() of ra with (0, 0, 1), (0, -1, 0), (1, -0, -0): every other product in it has a zero factor.)  The rows are solved
+// from c[0] = n.ca.x, c[1] = n.ca.y (for t1.ca.z), c[2] = t1.ca.x (for t2.ca.y), c[3] = t2.ca.z — the values cross() gave,
+// not a restatement from ra — and the oracle's chain fma(ca.x, w.x, fma(ca.y, w.y, fma(ca.z, w.z, sgn v[axis]))) is evaluated
+// without the term of component `axis`, the others in their places.  The set-up (aa = Ia ca, k) is the general row's, in full.
+// Why every stored value stays what the oracle computes (finite velocities; a diverged env is outside the claim):
+//   - fma(±0, w, s) is s for finite w unless s is itself a zero, and then it is a zero: leaving the term out can change the
+//     sign of an exactly zero vrel and nothing else.  A shared word differs from the one it stands for only where a
+//     component of ra is an exact zero, and then as a zero of the other sign: the same case.
+//   - dl = fma(-vrel, rk, target rk) is target rk whatever the sign of a zero vrel, unless target rk is a zero.  The friction
+//     rows' target is 0 and their dl is formed as the plain product vrel (-rk) (their records hold -rk: one v_mul_f32 in its
+//     32-bit encoding instead of an FMA with the product 0 rk for an addend): it is fma(-vrel, rk, +0) bit for bit unless it is
+//     a zero, where it can be -0 for the oracle's +0.  The normal row keeps target rk, which is -0 when dist + linear_slop
+//     is 0: there too dl can only be a zero of the other sign.
+//   - acc + dl with dl a zero of either sign is acc, including acc = +0; and acc is never -0: the impulses start from +0
+//     (a new contact) or from acc warmstart, and the clamp med3(acc + dl, lo, hi) returns a -0 only for acc + dl = -0 (which
+//     takes acc = dl = -0) or for a bound -0 that wins, which it cannot: the normal row's lo is +0 and a friction row's
+//     bounds are ∓lim with lim = mu acc_n >= +0, where med3 orders -0 below +0 and returns +0 for lim = +0 (oracle: med3f).
+//     (A warmstart factor of 0 would make a -0 of a negative friction impulse; the next acc is then still the oracle's by
+//     value.)  The impulse applied to the velocities is na - acc, formed after the clamp from equal values: every velocity
+//     update sees the oracle's bits.
+struct GRow { v3 aa; float rk, k; };      // (n: rk = 1 / k; t1, t2: see GPoint)
 struct GPoint {
-  GRow n, t1, t2;
-  float target, in, i1, i2, ima, mu;
+  GRow n, t1, t2;                          // t1.rk, t2.rk = -1 / k: a friction row's dl is vrel (-rk)
+  float c[4];                              // the rows' non-zero ca components (above)
+  float target, in, i1, i2, ima;
   int a, idx;
   bool valid;
 };
 
-__device__ __forceinline__ GRow make_grow(v3 d, v3 ra, float ima, const m3& Ia) {
+// the ground points' friction coefficient: one value for all of them, so no point or record carries it
+__device__ __forceinline__ float ground_mu(const srl_config& c) { return c.friction_rock * c.friction_ground; }
+
+__device__ __forceinline__ GRow make_grow(v3 d, v3 ra, float ima, const m3& Ia, v3& ca) {
   GRow r;
-  r.ca = cross(ra, d);
-  r.aa = mmul(Ia, r.ca);
+  ca = cross(ra, d);
+  r.aa = mmul(Ia, ca);
   const float k = ima + dot(cross(r.aa, ra), d);
   r.rk = 1.0f / k;
   r.k = k;
@@ -119,14 +152,16 @@ __device__ __forceinline__ void grow_apply(v3 aa, float ima, v3& v, v3& w, float
   va = fmaf(SGN < 0 ? -ima : ima, imp, va);
   w = madd(w, aa, imp);
 }
-// a ground row solved, from its constants and the product trk = target * rk (off the velocities' chain: the body lanes read it
-// from their records, cg_store)
+// a ground row solved, from its constants — c0, c1: the components of ca other than AXIS, in x, y, z order — and, for the normal
+// row, the product trk = target * rk (off the velocities' chain: the body lanes read it from their records, cg_store).  The
+// friction rows (AXIS != 2) are called with rk = -1 / k; their trk is not read.
 template <int AXIS, int SGN>
-__device__ __forceinline__ void grow_solve_t(v3 ca, v3 aa, float rk, float k, float ima, v3& v, v3& w, float trk, float& acc,
-                                             float lo, float hi, float& res) {
+__device__ __forceinline__ void grow_solve_t(float c0, float c1, v3 aa, float rk, float k, float ima, v3& v, v3& w, float trk,
+                                             float& acc, float lo, float hi, float& res) {
   float& va = AXIS == 0 ? v.x : AXIS == 1 ? v.y : v.z;
-  const float vrel = fmaf(ca.x, w.x, fmaf(ca.y, w.y, fmaf(ca.z, w.z, SGN < 0 ? -va : va)));
-  float dl = fmaf(-vrel, rk, trk);
+  const float w0 = AXIS == 0 ? w.y : w.x, w1 = AXIS == 2 ? w.y : w.z;
+  const float vrel = fmaf(c0, w0, fmaf(c1, w1, SGN < 0 ? -va : va));
+  float dl = AXIS != 2 ? vrel * rk : fmaf(-vrel, rk, trk);
   const float na = __builtin_amdgcn_fmed3f(acc + dl, lo, hi);
   dl = na - acc;
   acc = na;
@@ -134,30 +169,32 @@ __device__ __forceinline__ void grow_solve_t(v3 ca, v3 aa, float rk, float k, fl
   grow_apply<AXIS, SGN>(aa, ima, v, w, dl);
 }
 template <int AXIS, int SGN>
-__device__ __forceinline__ void grow_solve(const GRow& r, float ima, v3& v, v3& w, float target, float& acc, float lo,
-                                           float hi, float& res) {
-  grow_solve_t<AXIS, SGN>(r.ca, r.aa, r.rk, r.k, ima, v, w, target * r.rk, acc, lo, hi, res);
+__device__ __forceinline__ void grow_solve(float c0, float c1, const GRow& r, float ima, v3& v, v3& w, float target, float& acc,
+                                           float lo, float hi, float& res) {
+  grow_solve_t<AXIS, SGN>(c0, c1, r.aa, r.rk, r.k, ima, v, w, target * r.rk, acc, lo, hi, res);
 }
 
 __device__ __forceinline__ GPoint make_ground_point(const Lds& L, int b, int i) {
   const DevParams& P = *L.P;
   GPoint p;
   p.valid = false; p.a = b; p.idx = i;
-  p.in = 0.0f; p.i1 = 0.0f; p.i2 = 0.0f; p.target = 0.0f; p.ima = 0.0f; p.mu = 0.0f;
+  p.in = 0.0f; p.i1 = 0.0f; p.i2 = 0.0f; p.target = 0.0f; p.ima = 0.0f;
   const float* g = L.GM(b);
   if (i >= __float_as_int(g[0])) return p;
   p.valid = true;
   p.ima = L.BC(b)[0];
-  p.mu = P.c.friction_rock * P.c.friction_ground;
   const m3 Ia = ldm(L.IW(b));
   const int vid = __float_as_int(g[SRL_GM_VID + i]);
   const v3 pw = ld3(L.WV(b) + 3 * vid);
   const v3 ra = V(pw.x, pw.y, pw.z - P.c.collision_margin) - ld3(L.X(b));
   v3 n = V(0.0f, 0.0f, 1.0f), t1, t2;
   plane_space(n, t1, t2);   // (0, -1, 0), (1, -0, -0)
-  p.n = make_grow(n, ra, p.ima, Ia);
-  p.t1 = make_grow(t1, ra, p.ima, Ia);
-  p.t2 = make_grow(t2, ra, p.ima, Ia);
+  v3 cn, c1, c2;
+  p.n = make_grow(n, ra, p.ima, Ia, cn);
+  p.t1 = make_grow(t1, ra, p.ima, Ia, c1);
+  p.t2 = make_grow(t2, ra, p.ima, Ia, c2);
+  p.c[0] = cn.x; p.c[1] = cn.y; p.c[2] = c1.x; p.c[3] = c2.z;
+  p.t1.rk = -p.t1.rk; p.t2.rk = -p.t2.rk;
   p.target = contact_target(P, g[SRL_GM_DIST + i]);
   p.in = g[SRL_GM_IN + i]; p.i1 = g[SRL_GM_T1 + i]; p.i2 = g[SRL_GM_T2 + i];
   return p;
@@ -165,7 +202,7 @@ __device__ __forceinline__ GPoint make_ground_point(const Lds& L, int b, int i) 
 
 // one turn of a ground point: the body's velocities, three axis rows, write back
 template <bool WARM>
-__device__ __forceinline__ void ground_turn(const Lds& L, GPoint& p, float& res) {
+__device__ __forceinline__ void ground_turn(const Lds& L, GPoint& p, float mu, float& res) {
   const float ws = L.P->c.warmstart;
   v3 v, w;
   vw_load(L.VW(p.a), v, w);
@@ -175,10 +212,10 @@ __device__ __forceinline__ void ground_turn(const Lds& L, GPoint& p, float& res)
     grow_apply<1, -1>(p.t1.aa, p.ima, v, w, p.i1);
     grow_apply<0, 1>(p.t2.aa, p.ima, v, w, p.i2);
   } else {
-    grow_solve<2, 1>(p.n, p.ima, v, w, p.target, p.in, 0.0f, 1e30f, res);
-    const float lim = p.mu * p.in;
-    grow_solve<1, -1>(p.t1, p.ima, v, w, 0.0f, p.i1, -lim, lim, res);
-    grow_solve<0, 1>(p.t2, p.ima, v, w, 0.0f, p.i2, -lim, lim, res);
+    grow_solve<2, 1>(p.c[0], p.c[1], p.n, p.ima, v, w, p.target, p.in, 0.0f, 1e30f, res);
+    const float lim = mu * p.in;
+    grow_solve<1, -1>(p.c[2], p.c[1], p.t1, p.ima, v, w, 0.0f, p.i1, -lim, lim, res);
+    grow_solve<0, 1>(p.c[2], p.c[3], p.t2, p.ima, v, w, 0.0f, p.i2, -lim, lim, res);
   }
   vw_store(L.VW(p.a), v, w);
 }
@@ -189,7 +226,7 @@ __device__ __forceinline__ void ground_turn(const Lds& L, GPoint& p, float& res)
 // them under); here lane = body keeps (v, w) and the points' accumulated impulses in registers for the whole phase and reads
 // the rows' constants — made once per sub-step by the point lanes, as before — from LDS in the order it consumes them
 // (reads that depend on nothing the rows compute).  Same rows, same order per body, same expression trees: bit-identical.
-#define SRL_CG_WORDS 28      // per ground point: 7 float4 (layout: cg_store)
+#define SRL_CG_WORDS 20      // per ground point: 5 float4 (layout: cg_store)
 struct GBody {
   float acc[SRL_GMAXP][3];   // accumulated impulses (normal, tangent 1, tangent 2) of the body's ground points
   float ima;
@@ -201,46 +238,50 @@ struct GBody {
 __device__ __forceinline__ float4* cg_rec(const Lds& L, int b, int i) {   // aliases the world vertices, dead during the solve
   return (float4*)L.WV(0) + (SRL_CG_WORDS / 4) * (SRL_GMAXP * b + i);
 }
+// A record holds what the rows read and nothing else, in the order ground_point consumes it: the four ca values (GRow: no
+// zero words), aa, rk and k of each row (-1 / k for the friction rows) and the normal row's target rk.  No friction target (it is
+// 0, and its product with rk is not formed) and no mu (ground_mu: a uniform value).  20 words against 28: five reads a point
+// instead of seven, and in srl_k_step's sweeps 37 - 38 vector instructions a point instead of 40 - 41 (the fourth: 41 for 44).
+// Measured with the friction product: +1.8 % env steps/s in the 20-step window, +1.1 - 3.0 % over six episodes; the shorter
+// rows and records without it were no gain by the project's rule (profiles/ground_zero_terms_ab.txt).
 __device__ __forceinline__ void cg_store(const Lds& L, const GPoint& p) {
   float4* r = cg_rec(L, p.a, p.idx);
-  r[0] = make_float4(p.n.ca.x, p.n.ca.y, p.n.ca.z, p.n.rk);
-  r[1] = make_float4(p.n.aa.x, p.n.aa.y, p.n.aa.z, p.target * p.n.rk);
-  r[2] = make_float4(p.t1.ca.x, p.t1.ca.y, p.t1.ca.z, p.t1.rk);
-  r[3] = make_float4(p.t1.aa.x, p.t1.aa.y, p.t1.aa.z, p.n.k);
-  r[4] = make_float4(p.t2.ca.x, p.t2.ca.y, p.t2.ca.z, p.t2.rk);
-  r[5] = make_float4(p.t2.aa.x, p.t2.aa.y, p.t2.aa.z, p.t1.k);
-  r[6] = make_float4(p.t2.k, p.mu, 0.0f * p.t1.rk, 0.0f * p.t2.rk);   // (a friction row's target is 0: `target * rk` as grow_solve forms it)
+  r[0] = make_float4(p.c[0], p.c[1], p.n.rk, p.target * p.n.rk);
+  r[1] = make_float4(p.n.aa.x, p.n.aa.y, p.n.aa.z, p.n.k);
+  r[2] = make_float4(p.c[2], p.c[3], p.t1.rk, p.t2.rk);
+  r[3] = make_float4(p.t1.aa.x, p.t1.aa.y, p.t1.aa.z, p.t1.k);
+  r[4] = make_float4(p.t2.aa.x, p.t2.aa.y, p.t2.aa.z, p.t2.k);
 }
 
-struct GRec { f4 q[7]; };   // one ground point's row constants (cg_store)
+struct GRec { f4 q[5]; };   // one ground point's row constants (cg_store)
 
 template <bool WARM>
-__device__ __forceinline__ void ground_point(const GRec& R, GBody& gb, int i, float ws, v3& v, v3& w, float& res) {
-  const f4 q0 = R.q[0], q1 = R.q[1], q2 = R.q[2], q3 = R.q[3], q4 = R.q[4], q5 = R.q[5], q6 = R.q[6];
+__device__ __forceinline__ void ground_point(const GRec& R, GBody& gb, int i, float ws, float mu, v3& v, v3& w, float& res) {
+  const f4 q0 = R.q[0], q1 = R.q[1], q2 = R.q[2], q3 = R.q[3], q4 = R.q[4];
   if (WARM) {
     gb.acc[i][0] = gb.acc[i][0] * ws; gb.acc[i][1] = gb.acc[i][1] * ws; gb.acc[i][2] = gb.acc[i][2] * ws;
     grow_apply<2, 1>(V(q1.x, q1.y, q1.z), gb.ima, v, w, gb.acc[i][0]);
     grow_apply<1, -1>(V(q3.x, q3.y, q3.z), gb.ima, v, w, gb.acc[i][1]);
-    grow_apply<0, 1>(V(q5.x, q5.y, q5.z), gb.ima, v, w, gb.acc[i][2]);
+    grow_apply<0, 1>(V(q4.x, q4.y, q4.z), gb.ima, v, w, gb.acc[i][2]);
   } else {
-    grow_solve_t<2, 1>(V(q0.x, q0.y, q0.z), V(q1.x, q1.y, q1.z), q0.w, q3.w, gb.ima, v, w, q1.w, gb.acc[i][0], 0.0f, 1e30f, res);
-    const float lim = q6.y * gb.acc[i][0];
-    grow_solve_t<1, -1>(V(q2.x, q2.y, q2.z), V(q3.x, q3.y, q3.z), q2.w, q5.w, gb.ima, v, w, q6.z, gb.acc[i][1], -lim, lim, res);
-    grow_solve_t<0, 1>(V(q4.x, q4.y, q4.z), V(q5.x, q5.y, q5.z), q4.w, q6.x, gb.ima, v, w, q6.w, gb.acc[i][2], -lim, lim, res);
+    grow_solve_t<2, 1>(q0.x, q0.y, V(q1.x, q1.y, q1.z), q0.z, q1.w, gb.ima, v, w, q0.w, gb.acc[i][0], 0.0f, 1e30f, res);
+    const float lim = mu * gb.acc[i][0];
+    grow_solve_t<1, -1>(q2.x, q0.y, V(q3.x, q3.y, q3.z), q2.z, q3.w, gb.ima, v, w, 0.0f, gb.acc[i][1], -lim, lim, res);
+    grow_solve_t<0, 1>(q2.x, q2.y, V(q4.x, q4.y, q4.z), q2.w, q4.w, gb.ima, v, w, 0.0f, gb.acc[i][2], -lim, lim, res);
   }
 }
 
 __device__ __forceinline__ GRec cg_load(const float4* rec, int i) {
   GRec R;
 #pragma unroll
-  for (int k = 0; k < 7; ++k) { const float4 t = rec[7 * i + k]; R.q[k].x = t.x; R.q[k].y = t.y; R.q[k].z = t.z; R.q[k].w = t.w; }
+  for (int k = 0; k < 5; ++k) { const float4 t = rec[5 * i + k]; R.q[k].x = t.x; R.q[k].y = t.y; R.q[k].z = t.z; R.q[k].w = t.w; }
   return R;
 }
 
 // ---- the record of point i + 1 requested while point i is computed (AHEAD).  A plain read whose only use sits in the guarded
 // block of the next point is sunk into that block by the compiler (at IR level), a volatile one becomes a flat load with a
 // wait behind it, an empty asm that pins the value waits for it: so the reads and their waits are written out.  cg_request
-// issues the seven 16-byte reads of record I (and passes `tie`, an operand the current point's first operation needs, through,
+// issues the five 16-byte reads of record I (and passes `tie`, an operand the current point's first operation needs, through,
 // so that the reads stand before that point's arithmetic); cg_arrive waits for everything in flight and passes the record and
 // `tie` (a result of the current point's last row) through, so that the wait stands behind that arithmetic and the next point's
 // in front of nothing it needs.  Every read is waited for in the block that issued it: no register is handed back to the
@@ -248,32 +289,29 @@ __device__ __forceinline__ GRec cg_load(const float4* rec, int i) {
 template <int I>
 __device__ __forceinline__ void cg_request(unsigned a, GRec& R, float& tie) {
   asm volatile(
-      "ds_read_b128 %0, %8 offset:%9\n\tds_read_b128 %1, %8 offset:%10\n\tds_read_b128 %2, %8 offset:%11\n\t"
-      "ds_read_b128 %3, %8 offset:%12\n\tds_read_b128 %4, %8 offset:%13\n\tds_read_b128 %5, %8 offset:%14\n\t"
-      "ds_read_b128 %6, %8 offset:%15"
-      : "=&v"(R.q[0]), "=&v"(R.q[1]), "=&v"(R.q[2]), "=&v"(R.q[3]), "=&v"(R.q[4]), "=&v"(R.q[5]), "=&v"(R.q[6]), "+v"(tie)
-      : "v"(a), "n"(112 * I), "n"(112 * I + 16), "n"(112 * I + 32), "n"(112 * I + 48), "n"(112 * I + 64), "n"(112 * I + 80),
-        "n"(112 * I + 96));
+      "ds_read_b128 %0, %6 offset:%7\n\tds_read_b128 %1, %6 offset:%8\n\tds_read_b128 %2, %6 offset:%9\n\t"
+      "ds_read_b128 %3, %6 offset:%10\n\tds_read_b128 %4, %6 offset:%11"
+      : "=&v"(R.q[0]), "=&v"(R.q[1]), "=&v"(R.q[2]), "=&v"(R.q[3]), "=&v"(R.q[4]), "+v"(tie)
+      : "v"(a), "n"(80 * I), "n"(80 * I + 16), "n"(80 * I + 32), "n"(80 * I + 48), "n"(80 * I + 64));
 }
 // the body's (v, w) and record 0 in one go (the compiler's own read of (v, w) would be waited for with a count that does not
 // know the records behind it: everything)
 __device__ __forceinline__ void cg_request_first(unsigned avw, unsigned a, f4& a0, f2& a1, GRec& R) {
   asm volatile(
-      "ds_read_b128 %0, %9\n\tds_read_b64 %1, %9 offset:16\n\t"
-      "ds_read_b128 %2, %10\n\tds_read_b128 %3, %10 offset:16\n\tds_read_b128 %4, %10 offset:32\n\t"
-      "ds_read_b128 %5, %10 offset:48\n\tds_read_b128 %6, %10 offset:64\n\tds_read_b128 %7, %10 offset:80\n\t"
-      "ds_read_b128 %8, %10 offset:96"
-      : "=&v"(a0), "=&v"(a1), "=&v"(R.q[0]), "=&v"(R.q[1]), "=&v"(R.q[2]), "=&v"(R.q[3]), "=&v"(R.q[4]), "=&v"(R.q[5]), "=&v"(R.q[6])
+      "ds_read_b128 %0, %7\n\tds_read_b64 %1, %7 offset:16\n\t"
+      "ds_read_b128 %2, %8\n\tds_read_b128 %3, %8 offset:16\n\tds_read_b128 %4, %8 offset:32\n\t"
+      "ds_read_b128 %5, %8 offset:48\n\tds_read_b128 %6, %8 offset:64"
+      : "=&v"(a0), "=&v"(a1), "=&v"(R.q[0]), "=&v"(R.q[1]), "=&v"(R.q[2]), "=&v"(R.q[3]), "=&v"(R.q[4])
       : "v"(avw), "v"(a));
 }
-__device__ __forceinline__ void cg_arrive_first(f4& a0, f2& a1, GRec& R) {   // the next record's seven reads stay in flight
-  asm volatile("s_waitcnt lgkmcnt(7)"
-               : "+v"(a0), "+v"(a1), "+v"(R.q[0]), "+v"(R.q[1]), "+v"(R.q[2]), "+v"(R.q[3]), "+v"(R.q[4]), "+v"(R.q[5]), "+v"(R.q[6]));
+__device__ __forceinline__ void cg_arrive_first(f4& a0, f2& a1, GRec& R) {   // the next record's five reads stay in flight
+  asm volatile("s_waitcnt lgkmcnt(5)"
+               : "+v"(a0), "+v"(a1), "+v"(R.q[0]), "+v"(R.q[1]), "+v"(R.q[2]), "+v"(R.q[3]), "+v"(R.q[4]));
 }
 template <int LEFT>   // LEFT: reads that may stay in flight (the record requested after this one)
 __device__ __forceinline__ void cg_arrive(GRec& R, float& tie) {
-  asm volatile("s_waitcnt lgkmcnt(%8)"
-               : "+v"(R.q[0]), "+v"(R.q[1]), "+v"(R.q[2]), "+v"(R.q[3]), "+v"(R.q[4]), "+v"(R.q[5]), "+v"(R.q[6]), "+v"(tie)
+  asm volatile("s_waitcnt lgkmcnt(%6)"
+               : "+v"(R.q[0]), "+v"(R.q[1]), "+v"(R.q[2]), "+v"(R.q[3]), "+v"(R.q[4]), "+v"(tie)
                : "n"(LEFT));
 }
 
@@ -282,19 +320,19 @@ __device__ __forceinline__ void cg_arrive(GRec& R, float& tie) {
 // sweep — sub-steps whose wave holds no pair point (half of all sub-steps, 20 - 85 % of the slowest envs') run their sweeps as the
 // ground phase alone, and nothing else reads or writes the velocities during the solve.
 template <bool WARM, bool AHEAD, bool KEEP>
-__device__ __forceinline__ void ground_body(GBody& gb, float ws, v3& v, v3& w, float& res) {
-  static_assert(SRL_CG_WORDS == 28, "cg_request reads seven float4 per record");
+__device__ __forceinline__ void ground_body(GBody& gb, float ws, float mu, v3& v, v3& w, float& res) {
+  static_assert(SRL_CG_WORDS == 20, "cg_request reads five float4 per record");
   const float4* rec = gb.rec;
   // The guards are nested: the points of a manifold are a prefix.
   static_assert(SRL_GMAXP == 4, "four nested guards below");
   if (!AHEAD) {
     if (!KEEP) vw_load(gb.pvw, v, w);
-    ground_point<WARM>(cg_load(rec, 0), gb, 0, ws, v, w, res);        // (a body lane is called with np >= 1)
+    ground_point<WARM>(cg_load(rec, 0), gb, 0, ws, mu, v, w, res);        // (a body lane is called with np >= 1)
     if (gb.np > 1) {
-      ground_point<WARM>(cg_load(rec, 1), gb, 1, ws, v, w, res);
+      ground_point<WARM>(cg_load(rec, 1), gb, 1, ws, mu, v, w, res);
       if (gb.np > 2) {
-        ground_point<WARM>(cg_load(rec, 2), gb, 2, ws, v, w, res);
-        if (gb.np > 3) ground_point<WARM>(cg_load(rec, 3), gb, 3, ws, v, w, res);
+        ground_point<WARM>(cg_load(rec, 2), gb, 2, ws, mu, v, w, res);
+        if (gb.np > 3) ground_point<WARM>(cg_load(rec, 3), gb, 3, ws, mu, v, w, res);
       }
     }
   } else {
@@ -310,19 +348,19 @@ __device__ __forceinline__ void ground_body(GBody& gb, float ws, v3& v, v3& w, f
     } else {
       cg_request<0>(ra, r0, w.z);
       cg_request<1>(ra, r1, w.z);
-      cg_arrive<7>(r0, w.z);
+      cg_arrive<5>(r0, w.z);
     }
-    ground_point<WARM>(r0, gb, 0, ws, v, w, res);
+    ground_point<WARM>(r0, gb, 0, ws, mu, v, w, res);
     cg_arrive<0>(r1, w.x);
     if (gb.np > 1) {
       cg_request<2>(ra, r2, w.z);
-      ground_point<WARM>(r1, gb, 1, ws, v, w, res);
+      ground_point<WARM>(r1, gb, 1, ws, mu, v, w, res);
       cg_arrive<0>(r2, w.x);
       if (gb.np > 2) {
         cg_request<3>(ra, r3, w.z);
-        ground_point<WARM>(r2, gb, 2, ws, v, w, res);
+        ground_point<WARM>(r2, gb, 2, ws, mu, v, w, res);
         cg_arrive<0>(r3, w.x);
-        if (gb.np > 3) ground_point<WARM>(r3, gb, 3, ws, v, w, res);
+        if (gb.np > 3) ground_point<WARM>(r3, gb, 3, ws, mu, v, w, res);
       }
     }
   }
@@ -354,6 +392,7 @@ __device__ __forceinline__ Point make_pair_point(const Lds& L, int sl, int i) {
   p.n = pack_row(make_row<true>(n, ra, rb, p.ima, Ia, p.imb, Ib), p.ima, p.imb);
   p.t1 = pack_row(make_row<true>(t1, ra, rb, p.ima, Ia, p.imb, Ib), p.ima, p.imb);
   p.t2 = pack_row(make_row<true>(t2, ra, rb, p.ima, Ia, p.imb, Ib), p.ima, p.imb);
+  p.t1.rk = -p.t1.rk; p.t2.rk = -p.t2.rk;   // (prow_solve<FRICTION>)
   p.target = contact_target(P, q[9]);
   p.in = q[10]; p.i1 = q[11]; p.i2 = q[12];
   return p;
@@ -376,10 +415,10 @@ __device__ __forceinline__ void point_turn(const Lds& L, Point& p, float& res) {
     prow_apply(p.t1, u, p.i1);
     prow_apply(p.t2, u, p.i2);
   } else {
-    prow_solve(p.n, u, p.target, p.in, 0.0f, 1e30f, res);
+    prow_solve<false>(p.n, u, p.target, p.in, 0.0f, 1e30f, res);
     const float lim = p.mu * p.in;
-    prow_solve(p.t1, u, 0.0f, p.i1, -lim, lim, res);
-    prow_solve(p.t2, u, 0.0f, p.i2, -lim, lim, res);
+    prow_solve<true>(p.t1, u, 0.0f, p.i1, -lim, lim, res);
+    prow_solve<true>(p.t2, u, 0.0f, p.i2, -lim, lim, res);
   }
   vw_store(pa, u.a);
   vw_store(pb, u.b);
@@ -397,9 +436,11 @@ __device__ __forceinline__ void point_turn(const Lds& L, Point& p, float& res) {
 // (2, 3) points 2 and 3 — two register sets per lane, the turns unrolled — so a body's velocities stay in the lane's registers
 // from a pair's first turn to its second: one LDS hand-off in two is gone, and no register moves.  Both lanes of a pair are in
 // EXEC for every turn: membership comes from the slot's point count and colour, which the quad shares.
-// A turn is 45 vector instructions with one LDS read and write per pair of turns (point_turn: 67, four reads and four writes
+// A turn was 45 vector instructions with one LDS read and write per pair of turns (point_turn: 67, four reads and four writes
 // per turn): +10.6 % at the headline shape for the split alone, +14.5 % with the velocities kept (profiles/pair_split_experiment.md).
-struct HRow { f2 k[3], u[3]; float rk, kk; };   // one body's half of a row; kk = effective mass denominator, rk = 1 / kk
+// It is 43 now: a friction row's impulse is the plain product vrel (-rk) (hrow_solve<FRICTION>), and the product 0 rk that was
+// made in front of each friction row as the FMA's addend is gone (profiles/ground_zero_terms_ab.txt).
+struct HRow { f2 k[3], u[3]; float rk, kk; };   // one body's half of a row; kk = effective mass denominator, rk = 1 / kk (friction rows: -1 / kk)
 struct HSet { HRow n, t1, t2; float trk, in, i1, i2; };   // trk = target rk of the normal row (a friction row's target is 0)
 struct PSplit {
   HSet s0, s1;     // the lane pair's first and second point: points 2 h and 2 h + 1 of the manifold, h = (lane >> 1) & 1
@@ -446,6 +487,7 @@ __device__ __forceinline__ HSet make_hset(const Lds& L, const float* mp, int i, 
   s.n = make_hrow(n, r, im, I, side);
   s.t1 = make_hrow(t1, r, im, I, side);
   s.t2 = make_hrow(t2, r, im, I, side);
+  s.t1.rk = -s.t1.rk; s.t2.rk = -s.t2.rk;   // (hrow_solve<FRICTION>)
   s.trk = contact_target(P, q[9]) * s.n.rk;
   s.in = q[10]; s.i1 = q[11]; s.i2 = q[12];
   return s;
@@ -485,25 +527,18 @@ __device__ __forceinline__ void hrow_apply(const HRow& r, f2 (&u)[3], f2 d2) {  
 #pragma unroll
   for (int c = 0; c < 3; ++c) u[c] = fma2(r.u[c], d2, u[c]);
 }
+template <bool FRICTION>   // FRICTION: target 0, r.rk = -1 / kk, dl = vrel (-rk) (as prow_solve)
 __device__ __forceinline__ void hrow_solve(const HRow& r, f2 (&u)[3], float trk, float& acc, float lo, float hi, float& res) {
   const f2 s = fma2(r.k[0], u[0], fma2(r.k[1], u[1], r.k[2] * u[2]));   // A: (dot(d, va), dot(ca, wa)); B: minus its own
   float own = s.x + s.y;
   asm("" : "+v"(own));   // (kept from the vectoriser, as in prow_solve)
   const float vrel = own + quad_partner(own);
-  float dl = fmaf(-vrel, r.rk, trk);
+  float dl = FRICTION ? vrel * r.rk : fmaf(-vrel, r.rk, trk);
   const float na = __builtin_amdgcn_fmed3f(acc + dl, lo, hi);
   dl = na - acc;
   acc = na;
   res = fmaxf(res, fabsf(dl * r.kk));
   hrow_apply(r, u, F2(dl, dl));
-}
-
-// A friction row's target rk = 0 rk (prow_solve forms the same product; its sign is rk's).  Off the chain, and formed where it is
-// used: as plain C++ the compiler hoists the four products of a lane out of the sweeps into registers the kernel does not have.
-__device__ __forceinline__ float zero_times(float rk) {
-  float t;
-  asm volatile("v_mul_f32 %0, 0, %1" : "=v"(t) : "v"(rk));
-  return t;
 }
 
 // one turn of a lane pair on one of its points: three rows on the two bodies' velocities, each in its lane's registers
@@ -516,10 +551,10 @@ __device__ __forceinline__ void hset_turn(HSet& s, f2 (&u)[3], float mu, float w
     hrow_apply(s.t1, u, d1);
     hrow_apply(s.t2, u, d2);
   } else {
-    hrow_solve(s.n, u, s.trk, s.in, 0.0f, 1e30f, res);
+    hrow_solve<false>(s.n, u, s.trk, s.in, 0.0f, 1e30f, res);
     const float lim = mu * s.in;
-    hrow_solve(s.t1, u, zero_times(s.t1.rk), s.i1, -lim, lim, res);
-    hrow_solve(s.t2, u, zero_times(s.t2.rk), s.i2, -lim, lim, res);
+    hrow_solve<true>(s.t1, u, 0.0f, s.i1, -lim, lim, res);
+    hrow_solve<true>(s.t2, u, 0.0f, s.i2, -lim, lim, res);
   }
 }
 
@@ -568,9 +603,11 @@ __device__ __forceinline__ void pair_phase(PSplit& p, float ws, unsigned long lo
 template <bool WARM, int T, int PP, bool SOLO>
 __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb, Point (&pp)[PP], PSplit& sp, int ncol, int gslot,
                                              const int (&pslot)[PP], int gsweep, const unsigned long long (&cm)[2],
-                                             const unsigned long long (&cm2)[2]) {
+                                             const unsigned long long (&cm2)[2], float gmu) {
   // gslot / pslot: the turn a lane's point takes (ground: its index; colour phases: 4 * colour + index; -1: none)
   // PAIR_SPLIT: sp instead of pp / pslot; cm / cm2: the first two colours' lanes whose pair holds a first / a second point
+  // gmu: the ground points' friction coefficient (substep makes it once: read here, its scalar load would be waited for in
+  // front of the first ground point, and the record requested ahead with it)
   typedef Variant<T, PP> VA;
   static_assert(!SOLO || VA::SOLO, "a solo sweep in a variant that has none");
   float res = 0.0f;
@@ -586,12 +623,12 @@ __device__ __forceinline__ bool solver_sweep(const Lds& L, GPoint& gp, GBody& gb
     for (int i = 0; i < SRL_GMAXP; ++i) {
       const unsigned long long t = gm & (T0 << i);
       if (t == 0) break;
-      if (__builtin_amdgcn_inverse_ballot_w64(t)) ground_turn<WARM>(L, gp, res);
+      if (__builtin_amdgcn_inverse_ballot_w64(t)) ground_turn<WARM>(L, gp, gmu, res);
       __builtin_amdgcn_wave_barrier();
     }
   } else {
     v3 v, w;
-    if (gb.np > 0) ground_body<WARM, !WARM && VA::GROUND_AHEAD, false>(gb, L.P->c.warmstart, v, w, res);
+    if (gb.np > 0) ground_body<WARM, !WARM && VA::GROUND_AHEAD, false>(gb, L.P->c.warmstart, gmu, v, w, res);
     __builtin_amdgcn_wave_barrier();
   }
   int c0 = 0;
