@@ -122,6 +122,16 @@ int srl_render_heightmap(srl_env* env, const float* poses_dev, const int32_t* me
 /* O2 row: underside map(s) of one mesh (observer.py:262-277), host output float[2^orientation_freedom][h*w]. */
 int srl_get_object_map(srl_env* env, int32_t mesh_id, float* object_map);
 
+/* `StackEnv.render(mode='rgb_array')` (env.py:295-332; `TestStackEnv.render`, :558-596) of every env, on the device:
+ * overhead_dev [n][H][W][3] = the overhead map coloured by elevation (R = m / max(m), or m where the max is 0; B = 1 - R, both
+ * float32 values; G = 0.5, 0.5 + 0.1 inside the goal rectangle), object_dev [n][h][w][3] = the same of the object map on show
+ * (orientation 0 of the pending rock; with ordering_freedom of the first rock still unplaced, `n[0]` of env.py:563; the empty
+ * map when there is none; no goal).  The images are that function of exactly the arrays srl_get_maps returns.  Either
+ * pointer may be NULL.  dtype 0: float64, the reference's return type; 1: uint8 frames, x * 255 + 0.5 in double, clamped to
+ * 0 .. 255 and truncated.  Enqueued on `stream` like srl_step: it sees the maps of the steps before it there and does not
+ * synchronise. */
+int srl_render_rgb(srl_env* env, int32_t dtype, void* overhead_dev, void* object_dev, void* stream);
+
 /* Per-kernel HIP-event timing (bench.py's roofline leg).  enable != 0 brackets every kernel launch of
  * srl_reset/srl_step with events on the launch stream; srl_get_kernel_times synchronises and returns the
  * accumulated milliseconds and launch counts since the last call: index 0 = settle (K1+K4),

@@ -13,6 +13,7 @@
 #include "../../include/stackrl_hip.h"
 #include "settle.hip"
 #include "render.hip"
+#include "view.hip"
 
 namespace {
 
@@ -209,6 +210,11 @@ void layout(DevParams& P, int concurrent) {
   P.S_MISC = s; s += M_WORDS;
   P.S_PAIR = s; s += P.NP;                 // pair id -> (i | j << 16), filled once per launch (settle.hip pair_word)
   P.LDS_WORDS = P.BLOB + s;
+}
+
+// every pixel of an object map with no rock in view = elev_object(1.0), evaluated like the kernel does
+float empty_object_elevation(const DevParams& P) {
+  return P.obj_c1 - P.obj_c2 / (SRL_FAR + P.c.object_max_dimension * (0.5f - 1.0f));
 }
 
 hipEvent_t get_event(srl_env* env) {
@@ -740,8 +746,7 @@ int srl_get_maps(srl_env* env, float* height, float* object_map, int32_t* goal_r
           if (m >= 0) {
             HIP_TRY(hipMemcpy(o, env->d_objmap + (size_t)m * per, sizeof(float) * per, hipMemcpyDeviceToHost));
           } else {
-            // empty map = elev_object(1.0), evaluated like the kernel does
-            float e0 = P.obj_c1 - P.obj_c2 / (SRL_FAR + P.c.object_max_dimension * (0.5f - 1.0f));
+            const float e0 = empty_object_elevation(P);
             for (size_t kk = 0; kk < per; ++kk) o[kk] = e0;
           }
         }
@@ -783,6 +788,23 @@ int srl_render_heightmap(srl_env* env, const float* poses, const int32_t* mesh_i
              mesh_ids, n_bodies);
   SRL_LAUNCH(env, 1, srl_k_render, dim3(n), dim3(SRL_RENDER_THREADS), env->render_lds, st, env->P, (const float4*)env->d_stage_ext,
              SRL_MAX_BODIES, (uint8_t*)nullptr, (uint8_t*)nullptr, (float*)nullptr, (uint8_t*)nullptr, n_bodies, height);
+  HIP_TRY(hipGetLastError());
+  return SRL_OK;
+}
+
+int srl_render_rgb(srl_env* env, int32_t dtype, void* overhead, void* object, void* stream) {
+  if (!env) return fail(SRL_EINVAL, "null env");
+  if (dtype != SRL_VIEW_F64 && dtype != SRL_VIEW_U8) return fail(SRL_EINVAL, "srl_render_rgb: dtype must be 0 (float64) or 1 (uint8)");
+  if (!env->d_mh) return fail(SRL_ENOMESH, "srl_load_meshes must be called first");
+  if (!overhead && !object) return SRL_OK;
+  const DevParams& P = env->P;
+  ViewParams V;
+  V.H = P.H; V.objmap = P.objmap; V.hdr = P.hdr;
+  V.res = P.c.overhead_res; V.r = P.c.object_res; V.n_orient = P.n_orient; V.ordering = P.c.ordering_freedom;
+  V.obj_empty = empty_object_elevation(P);
+  const dim3 grid(P.c.n_envs), block(SRL_VIEW_THREADS);
+  if (dtype == SRL_VIEW_F64) hipLaunchKernelGGL(srl_k_view, grid, block, 0, (hipStream_t)stream, V, (double*)overhead, (double*)object);
+  else hipLaunchKernelGGL(srl_k_view_u8, grid, block, 0, (hipStream_t)stream, V, (uint8_t*)overhead, (uint8_t*)object);
   HIP_TRY(hipGetLastError());
   return SRL_OK;
 }

@@ -46,6 +46,25 @@ def _np_ptr(a):
   return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
+# the image types of `render` -> srl_render_rgb's dtype codes (include/stackrl_hip.h)
+VIEW_DTYPES = {'float64': 0, 'uint8': 1}
+
+
+def _view_dtype(dtype):
+  """(srl_render_rgb code, torch dtype) of `render`'s dtype argument — a name, a torch or a numpy type; None = float64, what
+  the reference returns.  Code -1 for a type the export does not write."""
+  if dtype is None:
+    name = 'float64'
+  elif isinstance(dtype, torch.dtype):
+    name = str(dtype).split('.')[-1]
+  else:
+    try:
+      name = np.dtype(dtype).name
+    except TypeError:
+      name = str(dtype)
+  return VIEW_DTYPES.get(name, -1), TORCH_DTYPES.get(name)
+
+
 class VecStackEnv(object):
   """B independent Stack-v0 envs on one GPU (drop-in for `ParallelEnv`, utils.py:302)."""
 
@@ -318,6 +337,33 @@ class VecStackEnv(object):
                                             out.data_ptr(), self._stream()))
     return out
 
+  def render(self, mode='rgb_array', dtype=None, out=None):
+    """`StackEnv.render(mode='rgb_array')` (env.py:295-332; `TestStackEnv.render`, :558-596) of every env:
+    (rgb0 [B, H, H, 3], rgb1 [B, h, h, 3]) device tensors — the overhead map coloured by elevation with the goal rectangle
+    marked in the green channel, and the object map on show (orientation 0 of the pending rock; with ordering freedom of
+    the first rock still unplaced).  float64 like the reference's by default; dtype='uint8' gives frames.  The images are
+    those of the latest step, whether or not it has been waited for.  out: optional (rgb0, rgb1) tensors to write into."""
+    if mode != 'rgb_array':
+      raise ValueError("Invalid value {} for argument mode. Only 'rgb_array' is supported.".format(mode))
+    code, dt = _view_dtype(dtype)
+    if code < 0:     # the export refuses it, in its own words
+      _check(self._lib.srl_render_rgb(self._h, code, None, None, None))
+    shapes = ((self._B, self._H, self._H, 3), (self._B, self._hh, self._hh, 3))
+    if out is None:
+      out = tuple(torch.empty(s, dtype=dt, device=self._device) for s in shapes)
+    rgb0, rgb1 = out
+    for t, s in zip((rgb0, rgb1), shapes):
+      if tuple(t.shape) != s or t.dtype != dt or t.device != self._device or not t.is_contiguous():
+        raise ValueError('out must be contiguous {} tensors of shapes {} and {} on {}'.format(dt, shapes[0], shapes[1], self._device))
+    self._fork()
+    with torch.cuda.device(self._device):
+      _check(self._lib.srl_render_rgb(self._h, code, rgb0.data_ptr(), rgb1.data_ptr(), self._stream()))
+    if self._side is not None:
+      for t in (rgb0, rgb1):
+        t.record_stream(self._side)
+    self._join()
+    return rgb0, rgb1
+
   def set_profiling(self, enable=True):
     _check(self._lib.srl_set_profiling(self._h, int(bool(enable))))
 
@@ -451,6 +497,18 @@ class PipelinedVecStackEnv(object):
 
   def maps(self):
     return tuple(np.concatenate(x) for x in zip(*[e.maps() for e in self._envs]))
+
+  def render(self, mode='rgb_array', dtype=None):
+    """`VecStackEnv.render` of the whole batch, in env order: every group writes its slice, after its own latest step."""
+    if mode != 'rgb_array':
+      raise ValueError("Invalid value {} for argument mode. Only 'rgb_array' is supported.".format(mode))
+    e0 = self._envs[0]
+    dt = _view_dtype(dtype)[1] or torch.float64     # (a type the export refuses: the first group's call raises)
+    rgb0 = torch.empty((self._B, e0._H, e0._H, 3), dtype=dt, device=self._device)
+    rgb1 = torch.empty((self._B, e0._hh, e0._hh, 3), dtype=dt, device=self._device)
+    for k, e in enumerate(self._envs):
+      e.render(dtype=dtype, out=(rgb0[self._slice(k)], rgb1[self._slice(k)]))
+    return rgb0, rgb1
 
   def set_profiling(self, enable=True):
     for e in self._envs:
