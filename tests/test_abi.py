@@ -197,6 +197,49 @@ def test_rollout_conv_exports_refuse_bad_arguments_with_their_own_text():
     assert last().decode() == name + tail, (name, args)
 
 
+_X_PLAIN = 'srl_xcorr_mfma: bad arguments'
+_X_SHAPE = 'srl_xcorr_mfma: unsupported mode %d / shape %d, %d (128 / 32 and 64 / 16 are built)'
+_X_ROWS = 'srl_xcorr_rows: bad arguments (128 / 32 maps of at most 16 channels; bf16x3 needs float32 operands)'
+_X_BIG = 1 << 40      # scratch_bytes that any shape fits
+# (export, arguments without the stream, the whole text): one refused call per clause of the two checks of xcorr_mfma.hip
+_XCORR_REFUSED = [
+  # mode, precision, in, in_f32, kern, kern_f32, out, scratch, scratch_bytes, B, C, H, kh
+  ('srl_xcorr_mfma', (0, 0, None, 1, _P, 1, _P, _P, _X_BIG, 3, 16, 128, 32), _X_PLAIN),
+  ('srl_xcorr_mfma', (0, 0, _P, 1, _P, 1, _P, _P, _X_BIG, 0, 16, 128, 32), _X_PLAIN),
+  ('srl_xcorr_mfma', (0, 2, _P, 1, _P, 1, _P, _P, _X_BIG, 3, 16, 128, 32), _X_PLAIN),
+  ('srl_xcorr_mfma', (0, 0, _P, 1, _P, 1, _P, None, _X_BIG, 3, 16, 128, 32), _X_PLAIN),      # 3 samples of 16 channels: partials
+  ('srl_xcorr_mfma', (0, 0, _P, 1, _P, 1, _P, _P, _X_BIG, 3, 16, 100, 32), _X_SHAPE % (0, 100, 32)),
+  ('srl_xcorr_mfma', (3, 0, _P, 1, _P, 1, _P, _P, _X_BIG, 3, 16, 128, 32), _X_SHAPE % (3, 128, 32)),
+  ('srl_xcorr_mfma', (0, 0, _P, 1, _P, 1, _P, _P, 1024, 3, 16, 128, 32), 'srl_xcorr_mfma: scratch too small'),
+  ('srl_xcorr_mfma', (0, 1, _P, 0, _P, 1, _P, _P, _X_BIG, 3, 16, 128, 32),
+   'srl_xcorr_mfma: precision 1 (bf16x3) takes float32 operands'),
+  # precision, in, kern, f32, out, B, C, H, kh
+  ('srl_xcorr_rows', (0, _P, _P, 1, _P, 3, 17, 128, 32), _X_ROWS),
+  ('srl_xcorr_rows', (0, _P, _P, 1, _P, 3, 16, 64, 32), _X_ROWS),
+  ('srl_xcorr_rows', (1, _P, _P, 0, _P, 3, 16, 128, 32), _X_ROWS),
+  ('srl_xcorr_rows', (0, _P, _P, 1, None, 3, 16, 128, 32), _X_ROWS),
+]
+
+
+def test_xcorr_exports_refuse_bad_arguments_with_their_own_text():
+  """`srl_xcorr_mfma` and `srl_xcorr_rows` return 1 for arguments they refuse (before any HIP call: no GPU needed) and leave
+  their text behind `srl_xcorr_mfma_last_error`: one call per clause of their checks."""
+  from stackrl_amd import build, qops
+  build.build()
+  L = ctypes.CDLL(build.QLIB)
+  launching = {n for n, (res, _, err) in qops._SIGS.items() if err == qops._XCORR}
+  assert {n for n, _, _ in _XCORR_REFUSED} == launching and len(launching) == 2
+  last = L.srl_xcorr_mfma_last_error
+  last.restype, last.argtypes = ctypes.c_char_p, []
+  for name, args, text in _XCORR_REFUSED:
+    res, argtypes, _ = qops._SIGS[name]
+    f = getattr(L, name)
+    f.restype, f.argtypes = res, argtypes
+    assert len(args) + 1 == len(argtypes), name
+    assert f(*args, None) == 1, (name, args)
+    assert last().decode() == text, (name, args)
+
+
 def test_config_struct_matches_header():
   from stackrl_amd.config import CConfig, StackConfig
   with open(os.path.join(ROOT, 'include', 'srl_types.h')) as f:

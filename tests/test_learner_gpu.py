@@ -1200,9 +1200,8 @@ def test_rollout_argmax_against_float64_on_real_observations():
 @pytest.mark.parametrize('B,C,dt', XCORR_ROWS_CASES)
 def test_xcorr_row_product_forward(B, C, dt, monkeypatch):
   """The rollout's cross-correlation forward as a product per map row (csrc/xcorr_mfma.hip: Hankel fragments of the row x the
-  kernel's rows, the sum over kernel rows along a diagonal by DPP lane shifts) — here the default four-wave kernel
-  `k_xcorr_rows4`; the eight-wave `k_xcorr_rows` behind SRL_XCORR_ROWS_WAVES=8 runs in tests/test_xcorr_exact_gpu.py, which
-  holds both to exact results at every channel grouping: against the library formulation in float64 at the kernel family's
+  kernel's rows, the sum over kernel rows along a diagonal by DPP lane shifts), the four-wave kernel `k_xcorr_rows4`
+  (tests/test_xcorr_exact_gpu.py holds it to exact results at every channel grouping): against the library formulation in float64 at the kernel family's
   stated tolerances, against the Toeplitz kernel it replaces for large batches, bit-identical on repetition, and chosen by
   batch size (>= 192 samples) when nothing forces it."""
   from stackrl_amd import nets, qops

@@ -2,9 +2,8 @@
 
 The operands (tests/xcorr_cases.py) are chosen so that every product and every partial sum of any order is a float32 value:
 the Toeplitz family `k_xcorr_mfma` in its three modes, both geometries, every operand dtype pair and both precisions, with one
-channel or several per workgroup and with one channel group or several; the row-product forwards `k_xcorr_rows4` and
-`k_xcorr_rows` (SRL_XCORR_ROWS_WAVES=8) at every channel count their channel groups turn on; `srl_xcorr_rows`; and the autograd
-function under bf16 features all have to return `xcorr_cases.expect` exactly, and the same bits when run again.  A wrong tap,
+channel or several per workgroup and with one channel group or several; the row-product forward `k_xcorr_rows4` at every
+channel count its channel groups turn on; `srl_xcorr_rows`; and the autograd function under bf16 features all have to return `xcorr_cases.expect` exactly, and the same bits when run again.  A wrong tap,
 column, channel, sample offset, lo plane or rounding shows as a mismatch at a named output element; there is no tolerance to
 hide behind.  The one tolerance of the file is the rounding case at the end: dense random float32 operands at precision 0
 against the float64 correlation of the operands rounded to bf16, at the project's bound for exact bf16 operands.
@@ -27,12 +26,12 @@ TOEPLITZ_BC = [(3, 16), (3, 1), (32, 16)]
 PAIRS = [('f32', 'f32'), ('bf16', 'bf16'), ('f32', 'bf16'), ('bf16', 'f32')]      # (map, kernel) at precision 0
 SPLIT_BC = [(3, 16), (32, 16)]                                                      # precision 1
 LARGE_BATCH, LARGE_DISTINCT = 256, 5        # one channel group by the batch size: 256 samples cycling through five
-ROWS_CHANNELS = [1, 4, 5, 8, 9, 15, 16]     # around `c < C` and `min(wave + NW ci, C - 1)` of both row-product kernels
+ROWS_CHANNELS = [1, 4, 5, 8, 9, 15, 16]     # around `c < C` of the row-product kernel's channel groups (wave + 4 ci, tid / 32 + 8 h)
 ROWS_KINDS = ['f32x3', 'f32', 'bf16']       # float32 with the split (split operands), float32 and bf16 at precision 0 (integers)
-ROWS_WAVES = ['4', '8']                     # k_xcorr_rows4 (the default), k_xcorr_rows
+FOUR_WAVES = '4-%s'                         # case ids name the four-wave kernel, as they did while an eight-wave one ran beside it
 ROWS_BATCH = 192                            # the smallest batch that takes the row-product kernel unforced
 ROWS_ENTRY_BC = [(1, 5), (1, 16), (3, 5), (3, 16)]
-# the rounding case: the forward with two channels per workgroup, the gradients, the row-product kernels
+# the rounding case: the forward with two channels per workgroup, the gradients, the row-product kernel
 ROUNDING_FORWARD = [(20, 16, 128, 32), (20, 16, 64, 16)]
 ROUNDING_GRADIENTS = [(3, 16, 128, 32), (3, 16, 64, 16)]
 
@@ -134,7 +133,7 @@ def test_toeplitz_forward_with_one_channel_group(H, h, kind, monkeypatch):
   assert_exact(qops.xcorr_forward_mfma(x, w, int(kind == 'f32x3')), got, 'run again')
 
 
-# ================================================================================================ the row-product kernels
+# ================================================================================================ the row-product kernel
 def _rows_operands(kind, B, C):
   case = (XC.split_case if kind == 'f32x3' else XC.int_case)(B, C, 128, 32)
   x, w = case['x'].cuda(), case['w'].cuda()
@@ -144,16 +143,14 @@ def _rows_operands(kind, B, C):
 
 
 @pytest.mark.parametrize('kind', ROWS_KINDS)
-@pytest.mark.parametrize('C', ROWS_CHANNELS)
-@pytest.mark.parametrize('waves', ROWS_WAVES)
-def test_row_product_kernels_at_every_channel_grouping(waves, C, kind, monkeypatch):
-  """`k_xcorr_rows4` (a wave computes channels wave + 4 ci, a thread stages tid / 32 and tid / 32 + 8) and `k_xcorr_rows`
-  (wave + 8 ci, tid / 32), forced at 3 samples; with integer operands the Toeplitz kernel has to give the same bits."""
+@pytest.mark.parametrize('C', ROWS_CHANNELS, ids=[FOUR_WAVES % C for C in ROWS_CHANNELS])
+def test_row_product_kernels_at_every_channel_grouping(C, kind, monkeypatch):
+  """`k_xcorr_rows4` (a wave computes channels wave + 4 ci, a thread stages tid / 32 and tid / 32 + 8), forced at 3 samples;
+  with integer operands the Toeplitz kernel has to give the same bits."""
   from stackrl_amd import qops
   monkeypatch.setenv('SRL_XCORR_ROWS', '1')
-  monkeypatch.setenv('SRL_XCORR_ROWS_WAVES', waves)
   case, x, w, prec = _rows_operands(kind, 3, C)
-  what = 'rows kernel of %s waves, %s, C %d' % (waves, kind, C)
+  what = 'rows kernel, %s, C %d' % (kind, C)
   got = qops.xcorr_forward_mfma(x, w, prec)
   assert_exact(got, XC.expect(case, 0), what)
   assert_exact(qops.xcorr_forward_mfma(x, w, prec), got, what + ', run again')
@@ -162,18 +159,16 @@ def test_row_product_kernels_at_every_channel_grouping(waves, C, kind, monkeypat
     assert_exact(qops.xcorr_forward_mfma(x, w, prec), got, what + ' against the Toeplitz kernel')
 
 
-@pytest.mark.parametrize('kind', ROWS_KINDS)
-@pytest.mark.parametrize('waves', ROWS_WAVES)
-def test_row_product_kernels_chosen_by_the_batch_size(waves, kind, monkeypatch):
+@pytest.mark.parametrize('kind', ROWS_KINDS, ids=[FOUR_WAVES % kind for kind in ROWS_KINDS])
+def test_row_product_kernels_chosen_by_the_batch_size(kind, monkeypatch):
   from stackrl_amd import qops
   monkeypatch.delenv('SRL_XCORR_ROWS', raising=False)
-  monkeypatch.setenv('SRL_XCORR_ROWS_WAVES', waves)
   case = (XC.split_case if kind == 'f32x3' else XC.int_case)(LARGE_DISTINCT, 16, 128, 32)
   x, w, want = _cycled(case, ROWS_BATCH)
   if kind == 'bf16':
     x, w = x.bfloat16(), w.bfloat16()
   got = qops.xcorr_forward_mfma(x, w, int(kind == 'f32x3'))
-  assert_exact(got, want, 'rows kernel of %s waves, %s, at %d samples' % (waves, kind, ROWS_BATCH))
+  assert_exact(got, want, 'rows kernel, %s, at %d samples' % (kind, ROWS_BATCH))
   assert_exact(qops.xcorr_forward_mfma(x, w, int(kind == 'f32x3')), got, 'run again')
 
 
@@ -184,7 +179,6 @@ def test_xcorr_forward_rows_entry(B, C, kind, monkeypatch):
   used as they are; a sample's map is the same alone and in a batch, which is what the entry is for."""
   from stackrl_amd import qops
   monkeypatch.delenv('SRL_XCORR_ROWS', raising=False)
-  monkeypatch.delenv('SRL_XCORR_ROWS_WAVES', raising=False)
   case, x, w, _ = _rows_operands(kind, B, C)
   got = qops.xcorr_forward_rows(x, w)
   assert_exact(got, XC.expect(case, 0), 'srl_xcorr_rows %s B %d C %d' % (kind, B, C))
@@ -243,10 +237,8 @@ def test_float32_operands_are_rounded_to_nearest_even_gradients(B, C, H, h, mode
   _rounding(case, mode, qops._xcorr_mfma(mode, 0, a, k, B, C, H, h), 'Toeplitz %s %d/%d B %d' % (('', 'd/dx', 'd/dw')[mode], H, h, B))
 
 
-@pytest.mark.parametrize('waves', ROWS_WAVES)
-def test_float32_operands_are_rounded_to_nearest_even_rows(waves, monkeypatch):
+def test_float32_operands_are_rounded_to_nearest_even_rows(monkeypatch):
   from stackrl_amd import qops
   monkeypatch.setenv('SRL_XCORR_ROWS', '1')
-  monkeypatch.setenv('SRL_XCORR_ROWS_WAVES', waves)
   case = XC.rounding_case(3, 16, 128, 32)
-  _rounding(case, 0, qops.xcorr_forward_mfma(case['x'].cuda(), case['w'].cuda(), 0), 'rows kernel of %s waves B 3' % waves)
+  _rounding(case, 0, qops.xcorr_forward_mfma(case['x'].cuda(), case['w'].cuda(), 0), 'rows kernel B 3')

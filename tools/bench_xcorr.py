@@ -13,9 +13,8 @@ x = torch.rand((B, 16, 128, 128), generator=g, device='cuda')
 w = torch.rand((B, 16, 32, 32), generator=g, device='cuda') - 0.3
 for name, a, k, prec in (('bf16x3', x, w, qops.BF16X3), ('bf16', x.to(torch.bfloat16), w.to(torch.bfloat16), qops.BF16)):
   outs = {}
-  for rows in ('0', '1', '8'):
-    os.environ['SRL_XCORR_ROWS'] = '0' if rows == '0' else '1'
-    os.environ['SRL_XCORR_ROWS_WAVES'] = '8' if rows == '8' else '4'
+  for rows in ('0', '1'):
+    os.environ['SRL_XCORR_ROWS'] = rows
     for _ in range(3):
       o = qops.xcorr_forward_mfma(a, k, prec)
     torch.cuda.synchronize()
@@ -26,5 +25,5 @@ for name, a, k, prec in (('bf16x3', x, w, qops.BF16X3), ('bf16', x.to(torch.bflo
     e1.record()
     torch.cuda.synchronize()
     outs[rows] = o
-    print('%s B=%d %s: %.1f us per launch' % (name, B, {'0': 'Toeplitz            ', '1': 'row product, 4 waves', '8': 'row product, 8 waves'}[rows], 1e3 * e0.elapsed_time(e1) / 20))
+    print('%s B=%d %s: %.1f us per launch' % (name, B, {'0': 'Toeplitz            ', '1': 'row product, 4 waves'}[rows], 1e3 * e0.elapsed_time(e1) / 20))
   print('  max |rows - toeplitz| / scale = %.2e' % (float((outs['0'] - outs['1']).abs().max()) / float(outs['0'].abs().max())))
