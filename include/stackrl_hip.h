@@ -132,6 +132,40 @@ int srl_get_object_map(srl_env* env, int32_t mesh_id, float* object_map);
  * synchronise. */
 int srl_render_rgb(srl_env* env, int32_t dtype, void* overhead_dev, void* object_dev, void* stream);
 
+/* ---- State records: save, restore and fork env states on the device (csrc/state.hip).
+ * One env's persistent state is a record of 32-bit words, four parts in this order, each starting on a multiple of 4 words:
+ * its header (episode machine, episode counter = RNG counter, goal, reward memory, episode list, script), the words of its
+ * blob (poses, velocities, manifolds), its height map [overhead_res^2] and the staged render records of its rocks
+ * [episode_length][stride][4].  The randomness is counter based (key = seed + env_index_offset + env index, counter = the
+ * header's episode counter), so a record written back continues bit for bit; the key belongs to the SLOT: a record forked
+ * into another env continues alike until that env's next reset, which draws the slot's own stream.  Not state: the
+ * parameters, the mesh table, the error flags, timing, the launch order.
+ *
+ * Host arithmetic only, no handle, no device: the words of a record and the word offset of each of its four parts for a
+ * configuration (n_envs and env_index_offset are not read).  Either output may be NULL. */
+int srl_state_layout(const srl_config* cfg, int64_t* words, int64_t* part_offsets4);
+/* What records must agree on to be written into this handle: the record layout, the size of the header, n_mesh and the
+ * contents of the mesh table (hashed by srl_load_meshes), the configuration fields that shape the state or the kernels'
+ * reading of it (episode_length, the resolutions, object_max_dimension, max_z, metric, goal_size_ratio, the reward scale and
+ * exponents, place_at_com, the two freedoms, obs_dtype) and the source hash of srl_build_info.  n_envs and env_index_offset
+ * are not part of it; the solver and physics parameters may differ between handles. */
+int srl_state_signature(srl_env* env, uint64_t* signature);
+/* Gathers the records of the envs idx_dev[0 .. n) (int32, device; NULL = all n = n_envs envs in order) into records_dev
+ * [n][words] and returns the handle's seed and sample counter (host pointers, either may be NULL).  Enqueued on `stream`
+ * like srl_step: no blocking copy, no allocation.  Refused with SRL_EINVAL while the staged records are stale: after
+ * srl_load_meshes, srl_set_body_state or srl_step_simulation and before the next step. */
+int srl_state_get(srl_env* env, const int32_t* idx_dev, int32_t n, void* records_dev, uint32_t* seed, uint32_t* sample_counter,
+                  void* stream);
+/* Env dst_idx_dev[i] takes record src_rec_dev[i] of records_dev, i < n (int32, device; NULL = i).  Records may repeat (a
+ * fork); the destinations must be distinct and the record indexes inside the buffer (the caller's duty); an env index
+ * outside the handle is skipped and reported by the next srl_sync_status.  A signature that is not the handle's own is
+ * refused before any launch.  Enqueued on `stream`. */
+int srl_state_set(srl_env* env, uint64_t signature, const int32_t* dst_idx_dev, const int32_t* src_rec_dev, int32_t n,
+                  const void* records_dev, void* stream);
+/* The handle's seed and sample counter, the episode counters left alone (srl_seed zeroes them): the rest of a full
+ * restore.  A seed other than the handle's waits for the device first, like srl_seed. */
+int srl_state_set_rng(srl_env* env, uint32_t seed, uint32_t sample_counter);
+
 /* Per-kernel HIP-event timing (bench.py's roofline leg).  enable != 0 brackets every kernel launch of
  * srl_reset/srl_step with events on the launch stream; srl_get_kernel_times synchronises and returns the
  * accumulated milliseconds and launch counts since the last call: index 0 = settle (K1+K4),

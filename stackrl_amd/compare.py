@@ -474,14 +474,18 @@ def write(fname, force=False, **kwargs):
 
 
 # ------------------------------------------------------------------------------------------------ test (test.py:723-919)
-def test(policies, num_steps=1000, seed=11, save=None, verbose=True, show=False, keep_values=False, plots=None, **env_kwargs):
+def test(policies, num_steps=1000, seed=11, save=None, verbose=True, show=False, keep_values=False, plots=None, with_env=None,
+         **env_kwargs):
   """The command (test.py:723-919, without the curriculum form): make the env from `env_kwargs` (`stackrl_amd.env.make`), `run`,
   `analyse`, update `results.csv` in the env's directory — lines of a run with more steps are kept (`priority=num_steps`) — and
   print the returns.  `save`: the base directory (a string), True for './data/test', None or False for no files.  `plots`
-  (default: as `save`) saves the plots with the files, into `<base>/<env path>/<seed>-<num_steps>/`.  Returns the analysis."""
+  (default: as `save`) saves the plots with the files, into `<base>/<env path>/<seed>-<num_steps>/`.  `with_env(env, policies)`
+  may return the policies to run once the env exists (policies that need it: `lookahead.LookaheadPolicy`).  Returns the analysis."""
   from stackrl_amd import env as envs
   env = envs.make(**env_kwargs)
   try:
+    if with_env is not None:
+      policies = with_env(env, policies)
     data = run(env, policies, num_steps=num_steps, seed=seed, keep_values=keep_values, verbose=verbose)
   finally:
     env.close()

@@ -14,6 +14,7 @@
 #include "settle.hip"
 #include "render.hip"
 #include "view.hip"
+#include "state.hip"
 
 namespace {
 
@@ -70,6 +71,7 @@ struct srl_env {
   // the records are made by the settle kernel's tail for the envs it steps; after a test hook has moved bodies behind its
   // back (srl_set_body_state, srl_step_simulation) the next render is preceded by srl_k_stage over the whole batch
   bool stage_dirty = false;
+  uint64_t mesh_hash = 0;     // of the arrays srl_load_meshes was given: part of the state signature (srl_state_signature)
   size_t step_lds = 0, render_lds = 0, objmap_lds = 0;
   bool profiling = false;
   std::vector<EventPair> pending;
@@ -210,6 +212,27 @@ void layout(DevParams& P, int concurrent) {
   P.S_MISC = s; s += M_WORDS;
   P.S_PAIR = s; s += P.NP;                 // pair id -> (i | j << 16), filled once per launch (settle.hip pair_word)
   P.LDS_WORDS = P.BLOB + s;
+}
+
+// FNV-1a over bytes, chained through `h` (the state signature and the mesh table's hash)
+uint64_t fnv1a(const void* data, size_t bytes, uint64_t h = 0xcbf29ce484222325ull) {
+  const unsigned char* p = (const unsigned char*)data;
+  for (size_t i = 0; i < bytes; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
+  return h;
+}
+
+// The state record of one env (state.hip) in 32-bit words: EnvHdr, the blob, the height map, the staged records, each part
+// on a multiple of 4 words.  Host arithmetic on a configuration alone; P needs derive() and layout() done.
+struct StateLayout { int64_t words, off[4], size[4]; };
+StateLayout state_layout(const DevParams& P) {
+  StateLayout s;
+  s.size[0] = ((int64_t)(sizeof(EnvHdr) / sizeof(int32_t)) + 3) & ~(int64_t)3;
+  s.size[1] = P.BLOB;                                                      // a multiple of 4 (layout)
+  s.size[2] = (int64_t)P.c.overhead_res * P.c.overhead_res;                // overhead_res is a multiple of 8 (derive)
+  s.size[3] = (int64_t)P.c.episode_length * SRL_STAGE_STRIDE * 4;
+  s.words = 0;
+  for (int k = 0; k < 4; ++k) { s.off[k] = s.words; s.words += s.size[k]; }
+  return s;
 }
 
 // every pixel of an object map with no rock in view = elev_object(1.0), evaluated like the kernel does
@@ -498,6 +521,14 @@ int srl_load_meshes(srl_env* env, const float* verts, const int32_t* vert_off, c
   P.mh = env->d_mh; P.mv = env->d_mv; P.mt = env->d_mt; P.mp = env->d_mp; P.objmap = env->d_objmap; P.objmap_u8 = env->d_objmap_u8;
   P.n_mesh = n_mesh;
   P.VS = vs;
+  {   // the mesh table's contents as one number: records of another pool are refused (srl_state_set)
+    uint64_t h = fnv1a(&n_mesh, sizeof n_mesh);
+    h = fnv1a(vert_off, sizeof(int32_t) * ((size_t)n_mesh + 1), h);
+    h = fnv1a(verts, sizeof(float) * 3 * (size_t)vert_off[n_mesh], h);
+    h = fnv1a(tri_off, sizeof(int32_t) * ((size_t)n_mesh + 1), h);
+    h = fnv1a(tris, sizeof(int32_t) * 3 * (size_t)tri_off[n_mesh], h);
+    env->mesh_hash = fnv1a(mass_com, sizeof(float) * 4 * (size_t)n_mesh, h);
+  }
   env->P_dirty = true;
   env->stage_dirty = true;     // (records made from another mesh table are stale)
   int old_blob = P.BLOB;
@@ -649,6 +680,7 @@ int srl_sync_status(srl_env* env, void* stream) {
   if (f & 1) return fail(SRL_EINVAL_ACTION, "Invalid action.");
   if (f & 2) return fail(SRL_ESIM_DIVERGED, "Maximum number of simulator steps reached. This may be caused by incorrect behaviour due to a large time step value");
   if (f & 4) return fail(SRL_ESIM_DIVERGED, "More close rock pairs than manifold slots in some env (SRL_ST_PAIR_OVERFLOW): the step is not valid");
+  if (f & SRL_FLAG_STATE_INDEX) return fail(SRL_EINVAL, "srl_state_get / srl_state_set: an env index outside the handle, or a negative record index (that pair was skipped)");
   return SRL_OK;
 }
 
@@ -806,6 +838,119 @@ int srl_render_rgb(srl_env* env, int32_t dtype, void* overhead, void* object, vo
   if (dtype == SRL_VIEW_F64) hipLaunchKernelGGL(srl_k_view, grid, block, 0, (hipStream_t)stream, V, (double*)overhead, (double*)object);
   else hipLaunchKernelGGL(srl_k_view_u8, grid, block, 0, (hipStream_t)stream, V, (uint8_t*)overhead, (uint8_t*)object);
   HIP_TRY(hipGetLastError());
+  return SRL_OK;
+}
+
+// ---- state records (state.hip)
+
+int srl_state_layout(const srl_config* cfg, int64_t* words, int64_t* part_offsets) {
+  if (!cfg) return fail(SRL_EINVAL, "srl_state_layout: null config");
+  DevParams P;
+  memset(&P, 0, sizeof P);
+  P.c = *cfg;
+  const int rc = derive(P);
+  if (rc) return rc;
+  P.VS = 4;
+  layout(P, 0);   // (BLOB depends on episode_length alone)
+  const StateLayout s = state_layout(P);
+  if (words) *words = s.words;
+  if (part_offsets) for (int k = 0; k < 4; ++k) part_offsets[k] = s.off[k];
+  return SRL_OK;
+}
+
+int srl_state_signature(srl_env* env, uint64_t* signature) {
+  if (!signature) return fail(SRL_EINVAL, "srl_state_signature: null output");
+  if (!env) return fail(SRL_EINVAL, "srl_state_signature: null env");
+  if (!env->d_mh) return fail(SRL_ENOMESH, "srl_load_meshes must be called first (the mesh table is part of the signature)");
+  const DevParams& P = env->P;
+  const srl_config& c = P.c;
+  const StateLayout s = state_layout(P);
+  uint64_t h = fnv1a(&s, sizeof s);
+  const int64_t hdr_bytes = (int64_t)sizeof(EnvHdr);
+  h = fnv1a(&hdr_bytes, sizeof hdr_bytes, h);
+  h = fnv1a(&P.n_mesh, sizeof P.n_mesh, h);
+  h = fnv1a(&env->mesh_hash, sizeof env->mesh_hash, h);
+  // the fields that shape the state or the kernels' reading of it: the counts and resolutions, the metres a pixel and an
+  // elevation stand for, what the reward memory holds, the frame the poses are in, the observation the records render to.
+  // n_envs and env_index_offset are the handle's; the solver and physics parameters may differ between handles.
+  const int32_t ints[] = {c.episode_length, c.overhead_res, c.object_res, c.metric, c.reward_pexp, c.reward_oexp, c.place_at_com,
+                          c.orientation_freedom, c.ordering_freedom, c.obs_dtype};
+  const float floats[] = {c.object_max_dimension, c.max_z, c.goal_size_ratio, c.reward_scale};
+  h = fnv1a(ints, sizeof ints, h);
+  h = fnv1a(floats, sizeof floats, h);
+  const char* info = srl_build_info();   // "SRL_BUILD_INFO<variant|hash>": the hash of the sources
+  const char* bar = strchr(info, '|');
+  h = fnv1a(bar ? bar : info, strlen(bar ? bar : info), h);
+  *signature = h;
+  return SRL_OK;
+}
+
+namespace {
+// the grid of a state kernel: x = (env, record) pairs, y = chunks of a record, about SRL_STATE_BLOCKS workgroups in all (a
+// bandwidth kernel), both dimensions stride
+void state_launch_shape(const srl_env* env, int n, StateParts& S, dim3& grid) {
+  const DevParams& P = env->P;
+  const StateLayout s = state_layout(P);
+  S.hdr = (uint4*)P.hdr; S.blob = (uint4*)P.blob; S.H = (uint4*)P.H; S.stage = (uint4*)env->d_stage; S.flags = P.flags;
+  S.q_hdr = (int32_t)(s.size[0] / 4); S.q_blob = (int32_t)(s.size[1] / 4); S.q_H = (int32_t)(s.size[2] / 4); S.q_stage = (int32_t)(s.size[3] / 4);
+  S.n_envs = P.c.n_envs;
+  const int rounds = (int)((s.words / 4 + SRL_STATE_THREADS - 1) / SRL_STATE_THREADS);
+  const int gx = n < SRL_STATE_BLOCKS ? n : SRL_STATE_BLOCKS;
+  int gy = SRL_STATE_BLOCKS / gx;
+  if (gy > rounds) gy = rounds;
+  grid = dim3(gx, gy < 1 ? 1 : gy);
+}
+}  // namespace
+
+int srl_state_get(srl_env* env, const int32_t* idx_dev, int32_t n, void* records_dev, uint32_t* seed, uint32_t* sample_counter,
+                  void* stream) {
+  if (!records_dev) return fail(SRL_EINVAL, "srl_state_get: null records buffer");
+  if (n < 1) return fail(SRL_EINVAL, "srl_state_get: n must be at least 1");
+  if (!env) return fail(SRL_EINVAL, "srl_state_get: null env");
+  if (!env->d_mh) return fail(SRL_ENOMESH, "srl_load_meshes must be called first");
+  if (!idx_dev && n != env->P.c.n_envs) return fail(SRL_EINVAL, "srl_state_get: without indexes n must be the handle's n_envs");
+  if (env->stage_dirty)
+    return fail(SRL_EINVAL, "srl_state_get: the staged records are stale (no step since srl_load_meshes, srl_set_body_state or srl_step_simulation): step first");
+  StateParts S; dim3 grid;
+  state_launch_shape(env, n, S, grid);
+  hipLaunchKernelGGL(srl_k_state_get, grid, dim3(SRL_STATE_THREADS), 0, (hipStream_t)stream, S, idx_dev, (int)n, (uint4*)records_dev);
+  HIP_TRY(hipGetLastError());
+  if (seed) *seed = env->P.seed;
+  if (sample_counter) *sample_counter = env->P.sample_counter;
+  return SRL_OK;
+}
+
+int srl_state_set(srl_env* env, uint64_t signature, const int32_t* dst_idx_dev, const int32_t* src_rec_dev, int32_t n,
+                  const void* records_dev, void* stream) {
+  if (!records_dev) return fail(SRL_EINVAL, "srl_state_set: null records buffer");
+  if (n < 1) return fail(SRL_EINVAL, "srl_state_set: n must be at least 1");
+  if (!env) return fail(SRL_EINVAL, "srl_state_set: null env");
+  uint64_t own = 0;
+  const int rc = srl_state_signature(env, &own);
+  if (rc) return rc;
+  if (signature != own)
+    return fail(SRL_EINVAL, "srl_state_set: the records' signature is not this handle's (another record layout, mesh pool, configuration or library build)");
+  if (n > env->P.c.n_envs) return fail(SRL_EINVAL, "srl_state_set: more destinations than envs (they must be distinct)");
+  StateParts S; dim3 grid;
+  state_launch_shape(env, n, S, grid);
+  hipLaunchKernelGGL(srl_k_state_set, grid, dim3(SRL_STATE_THREADS), 0, (hipStream_t)stream, S, dst_idx_dev, src_rec_dev, (int)n,
+                     (uint4*)const_cast<void*>(records_dev));
+  HIP_TRY(hipGetLastError());
+  // the whole batch in index order brings its staged records along; after a partial set a stale batch stays stale (the next
+  // step makes every record again from the poses, the restored ones included)
+  if (!dst_idx_dev && n == env->P.c.n_envs) env->stage_dirty = false;
+  return SRL_OK;
+}
+
+int srl_state_set_rng(srl_env* env, uint32_t seed, uint32_t sample_counter) {
+  if (!env) return fail(SRL_EINVAL, "srl_state_set_rng: null env");
+  env->P.sample_counter = sample_counter;   // (read from the host copy only: srl_sample passes it by value)
+  if (seed != env->P.seed) {   // the settle kernels read the seed from the device copy of the parameters: as after srl_seed, the
+    // device is left idle and the next launch uploads the block
+    HIP_TRY(hipDeviceSynchronize());
+    env->P.seed = seed;
+    env->P_dirty = true;
+  }
   return SRL_OK;
 }
 

@@ -20,6 +20,7 @@ import torch
 from stackrl_amd import assets as _assets
 from stackrl_amd import lib as _lib
 from stackrl_amd import config as _config
+from stackrl_amd import state as _state
 from stackrl_amd.config import StackConfig
 
 TensorSpec = collections.namedtuple('TensorSpec', ['shape', 'dtype'])
@@ -118,6 +119,7 @@ class VecStackEnv(object):
     self._B, self._H, self._hh = B, H, h
     self._closed = False
     self._left = 0          # rocks of the running episode not yet placed (host mirror of the lock-step episode machine)
+    self._last = None       # the latest step's ((obs_map, obs_obj), reward, done): what `get_state` stores
     self._side = torch.cuda.Stream(device=self._device, priority=int(stream_priority or 0)) if side_stream else None
     self.seed(seed if seed is not None else 0)
 
@@ -223,6 +225,7 @@ class VecStackEnv(object):
     keys = self.config.reward_keys
     out = ((om, oo), torch.zeros(self._B if keys is None else (self._B, len(keys)), dtype=torch.float32, device=self._device),
            torch.zeros(self._B, dtype=torch.bool, device=self._device))     # utils.py:545-552
+    self._last = out
     wait = self._finish(out)
     block = self._block if block is None else block
     return wait() if block else wait
@@ -250,6 +253,7 @@ class VecStackEnv(object):
       for t in (om, oo, reward, done, action):
         t.record_stream(self._side)
     out = ((om, oo), reward, done.view(torch.bool))
+    self._last = out
     self._keep = action   # keep the action tensor alive until the kernels consumed it
     wait = self._finish(out)
     block = self._block if block is None else block
@@ -265,6 +269,100 @@ class VecStackEnv(object):
       a.record_stream(self._side)
     self._join()
     return a
+
+  # ---- states as values (stackrl_amd/state.py; csrc/state.hip)
+  def state_signature(self):
+    """`srl_state_signature`: what another handle must share with this one to take its records."""
+    sig = ctypes.c_uint64()
+    _check(self._lib.srl_state_signature(self._h, ctypes.byref(sig)))
+    return int(sig.value)
+
+  def _index_tensor(self, idx):
+    return None if idx is None else torch.as_tensor(idx, dtype=torch.int32).to(self._device).contiguous()
+
+  def _get_records(self, indexes=None):
+    """(records int32 [n, words] of the envs `indexes` (None = all), seed, sample counter), after the latest step on the
+    env's stream, with the fork / join of `render`."""
+    idx = self._index_tensor(indexes)
+    n = self._B if idx is None else int(idx.numel())
+    words = _state.layout(self.config)[0]
+    rec = torch.empty((n, words), dtype=torch.int32, device=self._device)
+    seed, counter = ctypes.c_uint32(), ctypes.c_uint32()
+    self._fork()
+    with torch.cuda.device(self._device):
+      _check(self._lib.srl_state_get(self._h, None if idx is None else idx.data_ptr(), n, rec.data_ptr(), ctypes.byref(seed),
+                                     ctypes.byref(counter), self._stream()))
+    if self._side is not None:
+      for t in (rec, idx):
+        if t is not None:
+          t.record_stream(self._side)
+    self._join()
+    return rec, int(seed.value), int(counter.value)
+
+  def _set_records(self, records, signature, dst=None, src=None):
+    """Env dst[i] takes record src[i] of `records` (None = i), `srl_state_set`; the indexes have been checked (`plan_set`)."""
+    records = records.to(device=self._device, dtype=torch.int32).contiguous()
+    d, s = self._index_tensor(dst), self._index_tensor(src)
+    n = int(d.numel()) if d is not None else (int(s.numel()) if s is not None else int(records.shape[0]))
+    self._fork()
+    with torch.cuda.device(self._device):
+      _check(self._lib.srl_state_set(self._h, ctypes.c_uint64(int(signature)), None if d is None else d.data_ptr(),
+                                     None if s is None else s.data_ptr(), n, records.data_ptr(), self._stream()))
+    if self._side is not None:
+      for t in (records, d, s):
+        if t is not None:
+          t.record_stream(self._side)
+    self._join()
+
+  def _host_extra(self, idx):
+    return {}
+
+  def _set_host_extra(self, extra, dst, src, whole):
+    pass
+
+  def get_state(self, indexes=None):
+    """The state of the envs `indexes` (None = all) after the latest step, as an `EnvState`: their records, the latest
+    step's observation, reward and done, and the host side of the episode machine.  Runs on the env's stream like `render`;
+    nothing is waited for.  Randomness belongs to the slot: env i draws from the key seed + env_index_offset + i with the
+    episode counter its record holds, so a record put into another slot (`set_state(..., indexes=...)`, `Lookahead`) continues
+    bit for bit until that slot's next reset, which draws the slot's own stream."""
+    if self._last is None:
+      raise RuntimeError('get_state needs a reset first')
+    idx = _state._index_list(indexes, 'indexes')
+    rec, seed, counter = self._get_records(idx)
+    (om, oo), r, d = self._last
+    if idx is None:
+      obs, r, d = (om.clone(), oo.clone()), r.clone(), d.clone()
+    else:
+      i = torch.as_tensor(idx, dtype=torch.int64, device=self._device)
+      obs, r, d = (om[i], oo[i]), r[i], d[i]
+    return _state.EnvState(rec, obs, r, d, self._left, seed, counter, self.state_signature(), self._host_extra(idx))
+
+  def set_state(self, state, indexes=None, source=None):
+    """Env indexes[i] takes record source[i] of `state` (None = i; records may repeat, the indexes may not) and the stored
+    `((obs_map, obs_obj), reward, done)` of the envs written is returned: the step tuple the env would have returned there.
+    With `indexes=None` the whole batch returns to the snapshot, its rocks-left count, seed and sample counter included.  A
+    partial set needs the snapshot at the env's own point of the episode (`ValueError` otherwise), and leaves the handle's
+    seed and sample counter alone.  `ValueError` too for a state of another configuration, pool or build, and for repeated
+    indexes.  The RNG key stays the slot's (see `get_state`)."""
+    dst, src, whole = _state.plan_set(state, self.state_signature(), self._left, self._B, indexes, source)
+    if not whole and self._last is None:
+      raise RuntimeError('a partial set_state needs a reset first')
+    state = state.to(self._device)
+    self._set_records(state.records, state.signature, dst, src)
+    out = state.step_tuple(src)
+    if whole:
+      _check(self._lib.srl_state_set_rng(self._h, state.seed, state.sample_counter))
+      self._left = state.left
+      self._last = out
+    else:
+      (om, oo), r, d = self._last
+      i = torch.as_tensor(dst, dtype=torch.int64, device=self._device)
+      om, oo, r, d = om.clone(), oo.clone(), r.clone(), d.clone()
+      om[i], oo[i], r[i], d[i] = out[0][0], out[0][1], out[1], out[2]
+      self._last = ((om, oo), r, d)
+    self._set_host_extra(state.extra, dst, src, whole)
+    return out
 
   # ---- telemetry (Simulator.poses / n_steps, Observer.state, Rewarder.goal)
   def state(self):
@@ -510,6 +608,61 @@ class PipelinedVecStackEnv(object):
       e.render(dtype=dtype, out=(rgb0[self._slice(k)], rgb1[self._slice(k)]))
     return rgb0, rgb1
 
+  def state_signature(self):
+    return self._envs[0].state_signature()
+
+  def _group_of(self, i):
+    for k in range(self._K):
+      if self._start[k] <= i < self._start[k + 1]:
+        return k
+    raise ValueError('indexes must be in [0, {})'.format(self._B))
+
+  def get_state(self, indexes=None):
+    """`VecStackEnv.get_state` of the whole batch (or of the envs `indexes`), group by group after `drain()`, in env order."""
+    self.drain()
+    idx = _state._index_list(indexes, 'indexes')
+    if idx is None:
+      parts, order = [e.get_state() for e in self._envs], None
+    else:
+      groups = [self._group_of(i) for i in idx]
+      parts, order = [], []
+      for k, e in enumerate(self._envs):
+        pos = [p for p, g in enumerate(groups) if g == k]
+        if pos:
+          parts.append(e.get_state([idx[p] - self._start[k] for p in pos]))
+          order += pos
+      order = torch.argsort(torch.as_tensor(order, dtype=torch.int64, device=self._device))   # concatenated -> asked-for order
+
+    def cat(f):
+      t = torch.cat([f(p) for p in parts])
+      return t if order is None else t[order]
+    p0 = parts[0]
+    return _state.EnvState(cat(lambda p: p.records), (cat(lambda p: p.obs[0]), cat(lambda p: p.obs[1])), cat(lambda p: p.reward),
+                           cat(lambda p: p.done), self._envs[0]._left, p0.seed, p0.sample_counter, p0.signature)
+
+  def set_state(self, state, indexes=None, source=None):
+    """`VecStackEnv.set_state` over the groups, after `drain()`: env indexes[i] of the whole batch takes record source[i]."""
+    self.drain()
+    e0 = self._envs[0]
+    dst, src, whole = _state.plan_set(state, e0.state_signature(), e0._left, self._B, indexes, source)
+    state = state.to(self._device)
+    if src is None:
+      src = list(range(len(state)))
+    for k, e in enumerate(self._envs):
+      if whole:
+        e.set_state(state, source=src[self._slice(k)])
+      else:
+        pos = [p for p, i in enumerate(dst) if self._group_of(i) == k]
+        if pos:
+          e.set_state(state, indexes=[dst[p] - self._start[k] for p in pos], source=[src[p] for p in pos])
+    o = self._outputs()      # the latest step is now the restored one
+    for k, e in enumerate(self._envs):
+      s = self._slice(k)
+      (om, oo), r, d = e._last
+      o['om'][s], o['oo'][s], o['reward'][s], o['done'][s] = om, oo, r, d.view(torch.uint8)
+    self._cur = o
+    return state.step_tuple(src)
+
   def set_profiling(self, enable=True):
     for e in self._envs:
       e.set_profiling(enable)
@@ -642,6 +795,38 @@ class StartedVecStackEnv(VecStackEnv):
     self._len_rng = np.random.RandomState(int(seed) % 2**32)   # the episode-length draws (env.py:387)
     return super(StartedVecStackEnv, self).seed(seed)
 
+  def _host_extra(self, idx):
+    kind, keys, pos, has_gauss, gauss = self._len_rng.get_state()
+    extra = {'since_reset': int(self._since_reset), 'len_rng_keys': torch.from_numpy(keys.astype(np.int64)), 'len_rng_pos': int(pos),
+             'len_rng_has_gauss': int(has_gauss), 'len_rng_gauss': float(gauss)}
+    if self._done_prev is not None:
+      extra['done_prev'] = self._done_prev.clone() if idx is None else self._done_prev[torch.as_tensor(idx, dtype=torch.int64, device=self._device)]
+    return extra
+
+  def _set_host_extra(self, extra, dst, src, whole):
+    prev = extra.get('done_prev')
+    if prev is not None:
+      prev = prev.to(self._device)
+      if src is not None:
+        prev = prev[torch.as_tensor(src, dtype=torch.int64, device=self._device)]
+      if whole:
+        self._done_prev = prev.clone()
+      elif self._done_prev is not None:
+        self._done_prev[torch.as_tensor(dst, dtype=torch.int64, device=self._device)] = prev
+    if whole:      # the batch's own fields: the episode-length generator and the step count since the reset
+      self._since_reset = int(extra['since_reset'])
+      self._len_rng.set_state(('MT19937', extra['len_rng_keys'].cpu().numpy().astype(np.uint32), int(extra['len_rng_pos']),
+                               int(extra['len_rng_has_gauss']), float(extra['len_rng_gauss'])))
+
+  def set_state(self, state, indexes=None, source=None):
+    """`VecStackEnv.set_state`, with the step count since the reset, the done flags of the step before and (whole batch only)
+    the state of the episode-length generator."""
+    if 'since_reset' not in state.extra:
+      raise ValueError('the state was not taken from a StartedVecStackEnv')
+    if indexes is not None and int(state.extra['since_reset']) != self._since_reset:
+      raise ValueError('a partial set_state needs the snapshot at the env\'s own point of the episode')
+    return super(StartedVecStackEnv, self).set_state(state, indexes=indexes, source=source)
+
   def _start_random(self, step, fresh):
     """Start placements of the envs `fresh` (bool [B]) marks as just reset, each with its own count drawn from
     [n_objects - episode_length, n_objects - min_episode_length] (env.py:384-387); the others are held."""
@@ -669,6 +854,7 @@ class StartedVecStackEnv(VecStackEnv):
       self._done_prev = out[2]
     else:
       out = self._start(out)
+    self._last = out
     block = self._block if block is None else block
     return out if block else (lambda: out)
 
@@ -679,10 +865,12 @@ class StartedVecStackEnv(VecStackEnv):
       fresh, self._done_prev = self._done_prev, out[2]
       if bool(fresh.any()):       # this call was the auto-reset of those envs (env.py:235-236)
         out = self._start_random(out, fresh)
+      self._last = out
       return out if block else (lambda: out)
     if self._since_reset == self.config.episode_length - self._n_start_steps:
       # every env is done: this call is the auto-reset (env.py:235-236), followed by the start placements
       out = self._start(super(StartedVecStackEnv, self).step(action, block=True))
+      self._last = out
       return out if block else (lambda: out)
     self._since_reset += 1
     return super(StartedVecStackEnv, self).step(action, block=block)

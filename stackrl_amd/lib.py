@@ -39,6 +39,11 @@ _SIGS = {
   'srl_build_info': (ctypes.c_char_p, []),
   'srl_get_stage_records': (ctypes.c_int, [_VP, _VP, ctypes.c_int64]),
   'srl_stage_record_stride': (ctypes.c_int32, []),
+  'srl_state_layout': (ctypes.c_int, [ctypes.POINTER(CConfig), _VP, _VP]),
+  'srl_state_signature': (ctypes.c_int, [_VP, _VP]),
+  'srl_state_get': (ctypes.c_int, [_VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP]),
+  'srl_state_set': (ctypes.c_int, [_VP, ctypes.c_uint64, _VP, _VP, ctypes.c_int32, _VP, _VP]),
+  'srl_state_set_rng': (ctypes.c_int, [_VP, ctypes.c_uint32, ctypes.c_uint32]),
 }
 EXPORTS = tuple(sorted(_SIGS))
 

@@ -5,6 +5,10 @@ and writes `results.csv` (and `data.npz`) under `--save`.
 
   python tools/compare_policies.py [--env Stack-v0] [--envs 16] [--num-steps 64] [--episode-length 8]
                                    [--baselines random,height,difference,corrcoef] [--weights FILE] [--save DIR] [--plots]
+                                   [--lookahead K]
+
+`--lookahead K` adds `<name>+look<K>` beside every policy: of the policy's own action and the K - 1 best other entries of its
+value map, the one whose simulated step gives the highest reward (stackrl_amd/lookahead.py).
 """
 import argparse
 import os
@@ -30,6 +34,7 @@ def main():
   ap.add_argument('--save', default=os.path.join('data', 'test'))
   ap.add_argument('--plots', action='store_true')
   ap.add_argument('--keep-values', action='store_true')
+  ap.add_argument('--lookahead', type=int, default=0, metavar='K', help='adds <name>+look<K> beside every policy')
   args = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit('compare_policies needs a HIP device')
@@ -48,8 +53,20 @@ def main():
     agent = DQN(net, collect_batch_size=args.envs, replay_memory_size=2 * args.envs, seed=0, policy_op=qops.FusedPolicy(fast=True),
                 xcorr='bf16x3')
     policies['dqn'] = lambda obs, n_valid=None: agent.greedy(obs, values=True, n_valid=n_valid)
+  looks = []
+
+  def with_lookahead(env, policies):
+    from stackrl_amd.lookahead import Lookahead, LookaheadPolicy
+    looks.append(Lookahead(env, args.lookahead))
+    out = {}
+    for name, p in policies.items():
+      out[name] = p
+      out['{}+look{}'.format(name, args.lookahead)] = LookaheadPolicy(p, looks[0])
+    return out
   res = compare.test(policies, num_steps=args.num_steps, seed=args.seed, save=args.save, plots=args.plots,
-                     keep_values=args.keep_values, **env_kwargs)
+                     keep_values=args.keep_values, with_env=with_lookahead if args.lookahead > 0 else None, **env_kwargs)
+  for look in looks:
+    look.close()
   np.set_printoptions(precision=3, suppress=True, linewidth=160)
   print('{:>12} {:>10} {:>10} {:>12} {:>12}'.format('policy', 'return', '+/-', 'action value', '+/-'))
   for row in zip(res['keys'], res['return'], res['return_std'], res['action_value'], res['action_value_std']):
