@@ -65,6 +65,29 @@ class MeshPool:
                         tri_off=self.tri_off, mass_com=self.mass_com,
                         names=np.array(self.names))
 
+  def write_directory(self, path):
+    """The pool as the reference keeps its assets (generator.py:186, :229-266): `<name>.obj` (`v` / `f` records),
+    `<name>.urdf` (the subset `load_obj_urdf` reads — mass, the inertial origin, lateral friction 0.6 — plus the inertia
+    about the centre of mass and the mesh file name) and `log.csv` (Name, Volume, Rectangularity, AspectRatio, NumVertices;
+    the box is the axis-aligned one, which for a generated rock is its oriented one).  Numbers are written with nine
+    significant digits, so `load_directory(path, '*')` gives the float32 arrays back."""
+    os.makedirs(path, exist_ok=True)
+    g = '{:.9g}'.format
+    with open(os.path.join(path, 'log.csv'), 'w') as log:
+      log.write('Name,Volume,Rectangularity,AspectRatio,NumVertices\n')
+      for i, name in enumerate(self.names):
+        v, t, mc = self.mesh(i)
+        with open(os.path.join(path, name + '.obj'), 'w') as f:
+          f.write(''.join('v {} {} {}\n'.format(g(p[0]), g(p[1]), g(p[2])) for p in v))
+          f.write(''.join('f {} {} {}\n'.format(a + 1, b + 1, c + 1) for a, b, c in t))
+        volume, _ = mass_properties(v.astype(np.float64), t)
+        ixx, ixy, ixz, iyy, iyz, izz = inertia(v, t, float(mc[0]))
+        with open(os.path.join(path, name + '.urdf'), 'w') as f:
+          f.write(_URDF.format(name=name, mass=g(mc[0]), x=g(mc[1]), y=g(mc[2]), z=g(mc[3]), ixx=g(ixx), ixy=g(ixy), ixz=g(ixz),
+                               iyy=g(iyy), iyz=g(iyz), izz=g(izz)))
+        ext = v.astype(np.float64).max(0) - v.astype(np.float64).min(0)
+        log.write('{},{},{},{},{}\n'.format(name, volume, volume / ext.prod(), ext.max() / ext.min(), len(v)))
+
   @classmethod
   def load(cls, path):
     z = np.load(path, allow_pickle=False)
@@ -156,6 +179,47 @@ def mass_properties(v, t):
   volume = vol6.sum() / 6.0
   com = ((a + b + c) * vol6[:, None]).sum(0) / (24.0 * volume)
   return volume, com
+
+
+def inertia(v, t, mass):
+  """(ixx, ixy, ixz, iyy, iyz, izz) of a closed triangle mesh of uniform density about its centre of mass (signed
+  tetrahedra: the second moments of the tetrahedron (0, a, b, c) are det / 120 (sum_p p p^T + (sum_p p)(sum_p p)^T))."""
+  v = np.asarray(v, dtype=np.float64)
+  a, b, c = v[t[:, 0]], v[t[:, 1]], v[t[:, 2]]
+  det = np.einsum('ij,ij->i', a, np.cross(b, c))
+  volume, com = mass_properties(v, t)
+  s = a + b + c
+  M = sum(np.einsum('n,ni,nj->ij', det, p, p) for p in (a, b, c, s)) / 120.0
+  C = M - volume * np.outer(com, com)
+  I = (mass / volume) * (np.trace(C) * np.eye(3) - C)
+  return I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]
+
+
+# what `MeshPool.write_directory` writes per rock: the fields `load_urdf` reads, the inertia and the mesh
+_URDF = """<?xml version="1.0"?>
+<robot name="{name}">
+  <link name="{name}">
+    <contact>
+      <lateral_friction value="0.6"/>
+    </contact>
+    <inertial>
+      <origin xyz="{x} {y} {z}"/>
+      <mass value="{mass}"/>
+      <inertia ixx="{ixx}" ixy="{ixy}" ixz="{ixz}" iyy="{iyy}" iyz="{iyz}" izz="{izz}"/>
+    </inertial>
+    <visual>
+      <geometry>
+        <mesh filename="{name}.obj"/>
+      </geometry>
+    </visual>
+    <collision>
+      <geometry>
+        <mesh filename="{name}.obj"/>
+      </geometry>
+    </collision>
+  </link>
+</robot>
+"""
 
 
 def _min_area_rect(p2):

@@ -120,6 +120,9 @@ class VecStackEnv(object):
     self._closed = False
     self._left = 0          # rocks of the running episode not yet placed (host mirror of the lock-step episode machine)
     self._last = None       # the latest step's ((obs_map, obs_obj), reward, done): what `get_state` stores
+    self._needs_reset = False     # `set_pool` has replaced the mesh table under the running episode
+    self._script_pending = False  # `set_script` has named mesh ids for the next reset
+    self._holds_at_reset = False  # an auto-reset call may hold some envs (`StartedVecStackEnv` with random lengths): their script stays
     self._side = torch.cuda.Stream(device=self._device, priority=int(stream_priority or 0)) if side_stream else None
     self.seed(seed if seed is not None else 0)
 
@@ -186,6 +189,32 @@ class VecStackEnv(object):
     if mesh_ids.shape != (self._B, self.config.episode_length) or goal_rect.shape != (self._B, 4):
       raise ValueError('script shapes must be [B, L] and [B, 4]')
     _check(self._lib.srl_set_script(self._h, _np_ptr(mesh_ids), _np_ptr(goal_rect)))
+    self._script_pending = True
+
+  def set_pool(self, pool):
+    """Load another `assets.MeshPool` into the live env (`srl_load_meshes` once more; it waits for the device): the
+    rocks of the next episodes come from it, e.g. a pool `rocks.generate_pool` has just made.  The bodies of the running
+    episode belong to the old mesh table, so `step` (and `render`, `step_simulation`) is refused until the next `reset`.
+    An episode script waiting for the next reset names meshes of the old table: `set_pool` refuses then (set the script
+    after it).  The state signature changes with the mesh table: states taken before are refused, a whole-batch `set_state` of
+    a state of the new table (a sibling env's) stands for the reset, and a `Lookahead` on this env reloads its scratch env
+    at its next `evaluate`."""
+    if len(pool) < 1:
+      raise AssertionError('List of object descriptor files is empty.')       # env.py:103
+    if self._script_pending:
+      raise RuntimeError('an episode script is waiting for the next reset: call set_script after set_pool')
+    with torch.cuda.device(self._device):
+      torch.cuda.synchronize(self._device)
+      _check(self._lib.srl_load_meshes(self._h, _np_ptr(pool.verts), _np_ptr(pool.vert_off), _np_ptr(pool.tris),
+                                       _np_ptr(pool.tri_off), _np_ptr(pool.mass_com), len(pool)))
+    self.pool = pool
+    self._left = 0
+    self._last = None
+    self._needs_reset = True
+
+  def _require_reset(self, what):
+    if self._needs_reset:
+      raise RuntimeError('{} after set_pool needs a reset first: the running episode belongs to the old pool'.format(what))
 
   # ---- stepping
   def _stream(self):
@@ -219,6 +248,7 @@ class VecStackEnv(object):
     with torch.cuda.device(self._device):
       _check(self._lib.srl_reset(self._h, om.data_ptr(), oo.data_ptr(), self._stream()))
     self._left = self.config.episode_length
+    self._needs_reset = self._script_pending = False
     if self._side is not None:      # the caching allocator must not hand these blocks out again while the side stream writes them
       for t in (om, oo):
         t.record_stream(self._side)
@@ -232,6 +262,7 @@ class VecStackEnv(object):
 
   def step(self, action, block=None, out=None):
     """out: optional (obs_map, obs_obj, reward, done uint8) tensors to write into (contiguous views of a larger batch)."""
+    self._require_reset('step')
     if not torch.is_tensor(action):
       action = torch.as_tensor(action)
     action = action.to(device=self._device, dtype=torch.int64).contiguous()
@@ -248,6 +279,8 @@ class VecStackEnv(object):
     with torch.cuda.device(self._device):
       _check(self._lib.srl_step(self._h, action.data_ptr(), om.data_ptr(), oo.data_ptr(), reward.data_ptr(),
                                 done.data_ptr(), self._stream()))
+    if self._left == 0 and not self._holds_at_reset:   # the auto-reset of every env has taken the script, as `reset` does
+      self._script_pending = False
     self._left = self.config.episode_length if self._left == 0 else self._left - 1   # env.py:235-236: auto-reset
     if self._side is not None:
       for t in (om, oo, reward, done, action):
@@ -355,6 +388,7 @@ class VecStackEnv(object):
       _check(self._lib.srl_state_set_rng(self._h, state.seed, state.sample_counter))
       self._left = state.left
       self._last = out
+      self._needs_reset = False       # (the signature has been checked: a whole episode of the table now loaded)
     else:
       (om, oo), r, d = self._last
       i = torch.as_tensor(dst, dtype=torch.int64, device=self._device)
@@ -398,6 +432,7 @@ class VecStackEnv(object):
 
   def step_simulation(self, n=1):
     """`pb.stepSimulation` x n on every env (no placement, no stop criterion, no render)."""
+    self._require_reset('step_simulation')
     _check(self._lib.srl_step_simulation(self._h, int(n), self._stream()))
     _check(self._lib.srl_sync_status(self._h, self._stream()))
 
@@ -446,6 +481,7 @@ class VecStackEnv(object):
     code, dt = _view_dtype(dtype)
     if code < 0:     # the export refuses it, in its own words
       _check(self._lib.srl_render_rgb(self._h, code, None, None, None))
+    self._require_reset('render')
     shapes = ((self._B, self._H, self._H, 3), (self._B, self._hh, self._hh, 3))
     if out is None:
       out = tuple(torch.empty(s, dtype=dt, device=self._device) for s in shapes)
@@ -577,6 +613,14 @@ class PipelinedVecStackEnv(object):
   def set_script(self, mesh_ids, goal_rect):
     for k, e in enumerate(self._envs):
       e.set_script(mesh_ids[self._slice(k)], goal_rect[self._slice(k)])
+
+  def set_pool(self, pool):
+    """`VecStackEnv.set_pool` of every group, after the steps in flight."""
+    self.drain()
+    for e in self._envs:
+      e.set_pool(pool)
+    self.pool = pool
+    self._cur = None
 
   def close(self):
     for e in self._envs:
@@ -777,6 +821,7 @@ class StartedVecStackEnv(VecStackEnv):
       raise ValueError('The default start policy needs dtype uint8 observations (got {}): pass start_policy.'.format(dtype))
     super(StartedVecStackEnv, self).__init__(n_parallel=n_parallel, episode_length=n_objects, **kwargs)
     self._n_start_steps = int(n_objects) - int(episode_length)
+    self._holds_at_reset = self._random_lengths
     self._done_prev = None
     if start_policy is None:
       from stackrl_amd import baselines
@@ -859,6 +904,7 @@ class StartedVecStackEnv(VecStackEnv):
     return out if block else (lambda: out)
 
   def step(self, action, block=None):
+    self._require_reset('step')       # (before the step count moves)
     block = self._block if block is None else block
     if self._random_lengths:
       out = super(StartedVecStackEnv, self).step(action, block=True)

@@ -1,7 +1,7 @@
 """One-step physics lookahead: what reward would each of k actions give, without taking any of them.
 
 `Lookahead(env, k)` holds a scratch `VecStackEnv` of B x k envs with `env`'s pool and configuration.  `evaluate(actions [B, k])`
-gathers env's B state records (csrc/state.hip), writes each k-fold into the scratch handle and runs one `step` there; `env`
+(after following a `set_pool` of the env: the scratch env loads the new pool too) gathers env's B state records (csrc/state.hip), writes each k-fold into the scratch handle and runs one `step` there; `env`
 itself is not touched.  Randomness belongs to the slot (stackrl_amd/state.py): a forked record continues bit for bit until
 its slot's next reset, so the result does not depend on the slot as long as the step is not the auto-reset — `evaluate`
 raises there.
@@ -59,12 +59,26 @@ class Lookahead(object):
   def close(self):
     self.scratch.close()
 
+  def _follow_pool(self):
+    """After `env.set_pool` the env's records name meshes of a table the scratch env does not have: the scratch env loads
+    the env's pool too, and whatever else keeps the signatures apart is an error."""
+    sig = self.env.state_signature()
+    if sig != self.signature:
+      if self.scratch.pool is not self.env.pool:
+        self.scratch.set_pool(self.env.pool)
+        self.signature = self.scratch.state_signature()
+      if sig != self.signature:
+        raise ValueError('the scratch env does not share the env\'s state signature')
+
   def evaluate(self, actions, observations=False):
     """actions int64 [B, k] -> (reward [B, k(, keys)], done [B, k]) of one step with each, plus with `observations`
     (obs_map [B, k, H, W, 2], obs_obj [B, k, ...]) in front.  `ValueError` at the auto-reset point (no rock left): there
     the step draws the next episode from the slot's stream."""
     env = self.env
-    left = env._envs[0]._left if hasattr(env, '_envs') else env._left
+    first = env._envs[0] if hasattr(env, '_envs') else env
+    first._require_reset('Lookahead.evaluate')
+    self._follow_pool()
+    left = first._left
     if left == 0:
       raise ValueError('Lookahead.evaluate at the auto-reset point: the next step resets the envs and its result depends on the slot')
     actions = torch.as_tensor(actions).to(device=self.scratch._device, dtype=torch.int64)
@@ -76,8 +90,9 @@ class Lookahead(object):
     else:
       records = env._get_records()[0]
     s = self.scratch
-    s._set_records(records, self.signature, None, self._source)
+    s._set_records(records, env.state_signature(), None, self._source)   # (the export refuses records of another signature)
     s._left = left
+    s._needs_reset = False      # every scratch env now holds a record of the table the scratch has
     (om, oo), r, d = s.step(actions.reshape(-1), block=True)
     shape = (self.B, self.k)
     out = (r.reshape(shape + tuple(r.shape[1:])), d.reshape(shape))
