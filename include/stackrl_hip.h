@@ -132,6 +132,52 @@ int srl_get_object_map(srl_env* env, int32_t mesh_id, float* object_map);
  * synchronise. */
 int srl_render_rgb(srl_env* env, int32_t dtype, void* overhead_dev, void* object_dev, void* stream);
 
+/* Perspective view of the pile itself, ray cast on the device (csrc/camera.hip): what `StackEnv(gui=True)` shows in
+ * pybullet's viewer (simulator.py:140-146, env.py:275-281) — the rocks on the grey ground (simulator.py:167-179), a white
+ * rectangle over the observable area and a green one over the goal (observer.py:423-426, rewarder.py:202-209). The definition,
+ * float32 with one rounding per written operation unless said otherwise; fma(a, b, c) is the fused a * b + c, and
+ * dot(a, b) = fma(a.x, b.x, fma(a.y, b.y, a.z * b.z)):
+ *   scene    the rocks are the env's nb placed bodies (the pending rock at the spawn pose is not drawn); the ground is z = 0.
+ *   camera   one for the whole call, handed over as finished vectors the host computes in double and rounds to float32: eye,
+ *            fwd (unit), right and up (already scaled by tan(fov / 2) * W / H and tan(fov / 2)); no trigonometry on the device.
+ *            Pixel (row i, column j) of the H x W image looks through its centre: s = float(2 j + 1) / float(W) - 1,
+ *            u = 1 - float(2 i + 1) / float(H), d = (fwd + s * right) + u * up per component.  d is not normalised, so the ray
+ *            parameter t is the depth along fwd, like a depth buffer's.
+ *   rock     face f (unit normal n_f, offset d_f in the body's centre-of-mass frame) of a body at position x, rotation R
+ *            (R from the quaternion as the solver makes it, row i of R . n = fma(R_i0, n.x, fma(R_i1, n.y, R_i2 * n.z))):
+ *            nw = R . n_f, dw = d_f + dot(nw, x); for a ray from o along d: den = dot(nw, d), num = dw - dot(nw, o),
+ *            t_f = num / den (the correctly rounded quotient).  t_in = max of t_f over the faces with den < 0 (the face
+ *            of the lowest index among equals is "the face that gave t_in"), t_out = min of t_f over those with den > 0; a
+ *            face with den == 0 and num < 0 makes the ray miss.  The ray from the eye hits the rock if t_in < t_out and
+ *            t_in > 0.  The nearest hit is the smallest t_in over the bodies, the lowest slot among equals.
+ *   ground   hit at t_g = -eye.z / d.z where d.z < 0; a rock wins where t_in < t_g.  A ray that hits neither is sky.
+ *   shading  colour = albedo * (ambient + (diffuse * max(0, dot(n, light))) * lit) per channel; light is the unit vector
+ *            towards the light.  Rock: albedo rock_rgb, n = nw of the face that gave t_in.  Ground: n = (0, 0, 1), albedo
+ *            0.8 grey; where the hit point p = eye + t * d (fma(t, d, eye) per component) lies in the observable square
+ *            [0, sx] x [0, sy], sx = sy = float(overhead_res) * pixel, the albedo is 0.5 * albedo + 0.5 (white), and where
+ *            it also lies in the goal rectangle [float(u) * pixel, float(u + h) * pixel] x [float(v) * pixel,
+ *            float(v + w) * pixel] (rewarder.py:205-206) that is blended again, 0.5 * albedo + 0.5 * (0, 1, 0).  lit = 1; with
+ *            `shadows` lit = 0 where the ray from p + 1e-4 * n (fma per component) along light passes through any rock
+ *            (t_in < t_out and t_out > 0, t_in = -inf and t_out = +inf before the first face).  Sky is sky_rgb.
+ *   uint8    x * 255 + 0.5 in double, clamped to 0 .. 255, truncated (the rule of the overhead frames above).
+ * Yaw and pitch are the host's business (stackrl_amd/camera.py); pybullet is on no machine of this project, so that
+ * convention is this build's own and is not pinned to the viewer's.
+ *
+ * Scene: with the four scene pointers NULL the env's own state (poses, mesh ids, body count, goal); otherwise explicit, in
+ * the layouts of the height-map hook above — poses_dev float[n][SRL_MAX_BODIES][7], mesh_ids_dev int32[n][SRL_MAX_BODIES],
+ * n_bodies_dev int32[n] — plus goal_rect_dev int32[n][4] = (u, v, h, w): all four set or all four NULL.
+ * Outputs, any of them NULL but not all: rgb_dev uint8[n][H][W][3]; depth_dev float[n][H][W], t of the hit, +inf for sky;
+ * ids_dev int32[n][H][W], the body slot, -1 ground, -2 sky.  Enqueued on `stream` like a step: it sees the steps before it there,
+ * does not synchronise, reads the env and writes only the outputs.  Refused with SRL_EINVAL: width or height outside
+ * 1 .. 1024, a non-finite camera value, fwd or light not unit to 1e-3, a partial scene, all outputs NULL. */
+typedef struct srl_camera {
+  float eye[3], fwd[3], right[3], up[3], light[3], ambient, diffuse, rock_rgb[3], sky_rgb[3];
+  int32_t width, height, shadows;
+} srl_camera;
+int srl_render_camera(srl_env* env, const srl_camera* cam, const float* poses_dev, const int32_t* mesh_ids_dev,
+                      const int32_t* n_bodies_dev, const int32_t* goal_rect_dev, uint8_t* rgb_dev, float* depth_dev,
+                      int32_t* ids_dev, void* stream);
+
 /* ---- State records: save, restore and fork env states on the device (csrc/state.hip).
  * One env's persistent state is a record of 32-bit words, four parts in this order, each starting on a multiple of 4 words:
  * its header (episode machine, episode counter = RNG counter, goal, reward memory, episode list, script), the words of its

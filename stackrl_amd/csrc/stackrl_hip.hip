@@ -4,6 +4,7 @@
 #include <hip/hip_ext.h>
 
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -14,6 +15,7 @@
 #include "settle.hip"
 #include "render.hip"
 #include "view.hip"
+#include "camera.hip"
 #include "state.hip"
 
 namespace {
@@ -837,6 +839,44 @@ int srl_render_rgb(srl_env* env, int32_t dtype, void* overhead, void* object, vo
   const dim3 grid(P.c.n_envs), block(SRL_VIEW_THREADS);
   if (dtype == SRL_VIEW_F64) hipLaunchKernelGGL(srl_k_view, grid, block, 0, (hipStream_t)stream, V, (double*)overhead, (double*)object);
   else hipLaunchKernelGGL(srl_k_view_u8, grid, block, 0, (hipStream_t)stream, V, (uint8_t*)overhead, (uint8_t*)object);
+  HIP_TRY(hipGetLastError());
+  return SRL_OK;
+}
+
+int srl_render_camera(srl_env* env, const srl_camera* cam, const float* poses, const int32_t* mesh_ids, const int32_t* n_bodies,
+                      const int32_t* goal_rect, uint8_t* rgb, float* depth, int32_t* ids, void* stream) {
+  if (!env || !cam) return fail(SRL_EINVAL, "srl_render_camera: null argument");
+  if (cam->width < 1 || cam->width > SRL_CAM_MAX_SIDE || cam->height < 1 || cam->height > SRL_CAM_MAX_SIDE)
+    return fail(SRL_EINVAL, "srl_render_camera: width and height must be in 1 .. 1024");
+  {
+    const float* f = cam->eye;   // the 23 floats of the struct, eye .. sky_rgb
+    static_assert(offsetof(srl_camera, width) == 23 * sizeof(float), "srl_camera: 23 floats, then the ints");
+    for (int k = 0; k < 23; ++k)
+      if (!isfinite(f[k])) return fail(SRL_EINVAL, "srl_render_camera: the camera holds a non-finite value");
+    const double ff = (double)cam->fwd[0] * cam->fwd[0] + (double)cam->fwd[1] * cam->fwd[1] + (double)cam->fwd[2] * cam->fwd[2];
+    const double ll = (double)cam->light[0] * cam->light[0] + (double)cam->light[1] * cam->light[1] + (double)cam->light[2] * cam->light[2];
+    if (fabs(sqrt(ff) - 1.0) > 1e-3 || fabs(sqrt(ll) - 1.0) > 1e-3)
+      return fail(SRL_EINVAL, "srl_render_camera: fwd and light must be unit vectors (to 1e-3)");
+  }
+  const int given = (poses != nullptr) + (mesh_ids != nullptr) + (n_bodies != nullptr) + (goal_rect != nullptr);
+  if (given != 0 && given != 4)
+    return fail(SRL_EINVAL, "srl_render_camera: the scene pointers (poses, mesh ids, body counts, goal rectangles) must be all set or all NULL");
+  if (!rgb && !depth && !ids) return fail(SRL_EINVAL, "srl_render_camera: all outputs are NULL");
+  if (!env->d_mh) return fail(SRL_ENOMESH, "srl_load_meshes must be called first");
+  const DevParams& P = env->P;
+  CamParams C;
+  C.cam = *cam;
+  C.hdr = P.hdr; C.blob = P.blob; C.mh = P.mh; C.mp = P.mp;
+  C.poses = poses; C.mesh_ids = mesh_ids; C.n_bodies = n_bodies; C.goal = goal_rect;
+  C.BLOB = P.BLOB; C.OFF_X = P.OFF_X; C.OFF_Q = P.OFF_Q; C.OFF_MESH = P.OFF_MESH; C.n_mesh = P.n_mesh;
+  C.max_bodies = given ? SRL_MAX_BODIES : P.c.episode_length;
+  C.px = P.px; C.sx = (float)P.c.overhead_res * P.px; C.sy = C.sx;
+  C.tiles_x = (cam->width + SRL_CAM_TW - 1) / SRL_CAM_TW;
+  C.tiles = C.tiles_x * ((cam->height + SRL_CAM_TH - 1) / SRL_CAM_TH);
+  C.rgb = rgb; C.depth = depth; C.ids = ids;
+  const long long blocks = (long long)C.tiles * P.c.n_envs;
+  if (blocks > 0x7fffffffLL) return fail(SRL_EINVAL, "srl_render_camera: more than 2^31 - 1 tiles in one call");
+  hipLaunchKernelGGL(srl_k_camera, dim3((unsigned)blocks), dim3(SRL_CAM_THREADS), 0, (hipStream_t)stream, C);
   HIP_TRY(hipGetLastError());
   return SRL_OK;
 }

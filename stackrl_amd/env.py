@@ -498,6 +498,67 @@ class VecStackEnv(object):
     self._join()
     return rgb0, rgb1
 
+  def _camera_call(self, c, scene, rgb, depth, ids):
+    """`srl_render_camera` with the struct `c` on the env's stream, with the fork / join of `render`; any tensor may be None."""
+    tensors = [t for t in tuple(scene or ()) + (rgb, depth, ids) if t is not None]
+    ptr = lambda t: None if t is None else t.data_ptr()
+    sp = [ptr(t) for t in scene] if scene is not None else [None] * 4
+    self._fork()
+    with torch.cuda.device(self._device):
+      _check(self._lib.srl_render_camera(self._h, ctypes.byref(c), sp[0], sp[1], sp[2], sp[3], ptr(rgb), ptr(depth), ptr(ids),
+                                         self._stream()))
+    if self._side is not None:
+      for t in tensors:
+        t.record_stream(self._side)
+    self._join()
+
+  def render_camera(self, width=320, height=240, camera=None, rgb=True, depth=False, ids=False, out=None, scene=None):
+    """A perspective view of every env's pile, ray cast on the device (`srl_render_camera`, include/stackrl_hip.h holds the
+    definition): the rocks on the grey ground, the observable square in white, the goal rectangle in green, shadows — what
+    the reference's `StackEnv(gui=True)` shows in its viewer.  A method of its own: `render` keeps the reference's modes.
+      camera  a `stackrl_amd.camera.Camera`; None = `Camera.reference(config)`, the reference's GUI view
+      rgb, depth, ids  which images to return, in this order (one tensor when one is asked for, else a tuple):
+              uint8 [B, height, width, 3]; float32 [B, height, width], the depth along the viewing direction, +inf for sky;
+              int32 [B, height, width], the body slot, -1 ground, -2 sky
+      out     tensors to fill in place of new ones: one per image asked for, in that order (views of a larger batch are fine)
+      scene   (poses float32 [B, 32, 7], mesh_ids int32 [B, 32], n_bodies int32 [B], goal_rect int32 [B, 4]) to draw instead
+              of the env's own state, arrays or device tensors (the layouts of `render_heightmap` plus the goal rectangles)
+    The images are those of the latest step, whether or not it has been waited for; the env is only read."""
+    from stackrl_amd import camera as _camera
+    self._require_reset('render_camera')
+    c = (camera if camera is not None else _camera.Camera.reference(self.config)).to_c(width, height)
+    want = (bool(rgb), bool(depth), bool(ids))
+    specs = [((self._B, c.height, c.width, 3), torch.uint8), ((self._B, c.height, c.width), torch.float32),
+             ((self._B, c.height, c.width), torch.int32)]
+    if out is not None:
+      out = list(out) if isinstance(out, (tuple, list)) else [out]
+      if len(out) != sum(want):
+        raise ValueError('out must hold one tensor per image asked for ({})'.format(sum(want)))
+    ok_size = 1 <= c.width <= 1024 and 1 <= c.height <= 1024     # (otherwise the export refuses, in its own words)
+    images = []
+    for k, (shape, dt) in enumerate(specs):
+      if not want[k]:
+        images.append(None)
+      elif out is not None:
+        t = out.pop(0)
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != self._device or not t.is_contiguous():
+          raise ValueError('out must be contiguous tensors on {}: {} {}'.format(self._device, dt, shape))
+        images.append(t)
+      else:
+        images.append(torch.empty(shape if ok_size else (0,), dtype=dt, device=self._device))
+    if scene is not None:
+      shapes = ((self._B, _config.MAX_BODIES, 7), (self._B, _config.MAX_BODIES), (self._B,), (self._B, 4))
+      dts = (torch.float32, torch.int32, torch.int32, torch.int32)
+      if len(scene) != 4:
+        raise ValueError('scene must be (poses, mesh_ids, n_bodies, goal_rect)')
+      scene = tuple(torch.as_tensor(a).to(device=self._device, dtype=dt).contiguous() for a, dt in zip(scene, dts))
+      for t, sh in zip(scene, shapes):
+        if tuple(t.shape) != sh:
+          raise ValueError('scene must have shapes {}'.format(shapes))
+    self._camera_call(c, scene, *images)
+    got = tuple(t for t in images if t is not None)
+    return got[0] if len(got) == 1 else got
+
   def set_profiling(self, enable=True):
     _check(self._lib.srl_set_profiling(self._h, int(bool(enable))))
 
@@ -651,6 +712,20 @@ class PipelinedVecStackEnv(object):
     for k, e in enumerate(self._envs):
       e.render(dtype=dtype, out=(rgb0[self._slice(k)], rgb1[self._slice(k)]))
     return rgb0, rgb1
+
+  def render_camera(self, width=320, height=240, camera=None, rgb=True, depth=False, ids=False, scene=None):
+    """`VecStackEnv.render_camera` of the whole batch, in env order: every group writes its slice, after its own latest step."""
+    want = (bool(rgb), bool(depth), bool(ids))
+    w, h = int(width), int(height)
+    if not (1 <= w <= 1024 and 1 <= h <= 1024) or not any(want):     # the first group's call raises, in the export's words
+      return self._envs[0].render_camera(width, height, camera, rgb, depth, ids, scene=None if scene is None else tuple(a[self._slice(0)] for a in scene))
+    specs = (((self._B, h, w, 3), torch.uint8), ((self._B, h, w), torch.float32), ((self._B, h, w), torch.int32))
+    full = [torch.empty(s, dtype=dt, device=self._device) for (s, dt), on in zip(specs, want) if on]
+    for k, e in enumerate(self._envs):
+      sl = self._slice(k)
+      e.render_camera(width, height, camera, rgb, depth, ids, out=[t[sl] for t in full],
+                      scene=None if scene is None else tuple(a[sl] for a in scene))
+    return full[0] if len(full) == 1 else tuple(full)
 
   def state_signature(self):
     return self._envs[0].state_signature()

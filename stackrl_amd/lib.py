@@ -29,6 +29,7 @@ _SIGS = {
   'srl_render_heightmap': (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
   'srl_get_object_map': (ctypes.c_int, [_VP, ctypes.c_int32, _VP]),
   'srl_render_rgb': (ctypes.c_int, [_VP, ctypes.c_int32, _VP, _VP, _VP]),
+  'srl_render_camera': (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
   'srl_set_profiling': (ctypes.c_int, [_VP, ctypes.c_int32]),
   'srl_get_kernel_times': (ctypes.c_int, [_VP, _VP, _VP]),
   'srl_get_order_kernel_times': (ctypes.c_int, [_VP, _VP, _VP]),
