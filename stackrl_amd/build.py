@@ -15,6 +15,7 @@ LIB = os.path.join(HERE, 'libstackrl_hip.so')
 QLIB = os.path.join(HERE, 'libstackrl_qnet.so')
 CLIB = os.path.join(HERE, 'libstackrl_compare.so')
 RLIB = os.path.join(HERE, 'libstackrl_rocks.so')
+VLIB = os.path.join(HERE, 'libstackrl_valueview.so')
 _BASE = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared']
 _WARN = ['-Wall', '-Wno-unused-function', '-Wno-unused-value', '-Wno-unused-result']
 # -ffp-contract=off: the solver/rasteriser definition is "one IEEE rounding per written operation"
@@ -152,6 +153,8 @@ LIBRARIES = {
 # `source_hash`, `stale`, `build_library`, `build` and `_bind.binding` go through it.
 ASSET_LIBRARIES = {
   'rocks': _library(RLIB, ['rocks.hip'], QFLAGS, ('no-slp',)),
+  # the frames of a visualised comparison run (include/stackrl_valueview.h); tests/test_valueview_abi.py holds its guard
+  'valueview': _library(VLIB, ['valueview.hip'], QFLAGS, ('no-slp',)),
 }
 QSRC = LIBRARIES['qnet'].sources
 

@@ -226,7 +226,7 @@ def _wait(step):
   return step() if callable(step) else step
 
 
-def run(env, policies, num_steps=1024, seed=11, keep_values=False, verbose=False):
+def run(env, policies, num_steps=1024, seed=11, keep_values=False, verbose=False, visualize=None):
   """`run` (test.py:150-353) on a vectorised env of B envs: each policy in turn drives the env for `num_steps` steps, after
   `env.seed(seed)` and `env.reset()` (:259-267), while every policy evaluates every observation.
 
@@ -240,7 +240,13 @@ def run(env, policies, num_steps=1024, seed=11, keep_values=False, verbose=False
 
   Returns a dict: `keys` [P]; `actions` [P, P * num_steps, B, 2], the pixel as (row, column) of the value map, uint8 or uint16;
   `action_values` float32 [P, P * num_steps, B], each map's maximum; `rewards` float32 and `dones` bool [P, num_steps, B];
-  `record`, float64 [R(P)]; `n_actions`; and with `keep_values` `values` float32 [P, P * num_steps, B, A]."""
+  `record`, float64 [R(P)]; `n_actions`; and with `keep_values` `values` float32 [P, P * num_steps, B, A].
+
+  visualize: None, or a callable `visualize(step, policy_index, frames)` called before every env step with the picture the
+  reference's `visualize=True` shows (test.py:282-317), drawn on the device (`stackrl_amd.valueview`): frames uint8
+  [n, FH, FW, 3], one per env of `visualize.envs` (default: every env), drawn by `visualize.view` (default: `ValueView()`);
+  `valueview.Recorder` is the standard one.  Its `close()`, if it has one, is called at the end.  What is returned does not
+  depend on it."""
   policies = _named(policies)
   keys = np.array(list(policies.keys()))
   P = _check_P(len(keys))
@@ -250,7 +256,11 @@ def run(env, policies, num_steps=1024, seed=11, keep_values=False, verbose=False
   vshape = (spec[0].shape[-3] - spec[1].shape[-3] + 1, spec[0].shape[-2] - spec[1].shape[-2] + 1)
   A = int(vshape[0] * vshape[1])
   B = int(env.batch_size)
-  stats = dev = None
+  stats = dev = view = shown = None
+  if visualize is not None:
+    from stackrl_amd import valueview
+    view = getattr(visualize, 'view', None) or valueview.ValueView()
+    shown = getattr(visualize, 'envs', None)
   pixels, amaxes, kept, rewards, dones = [], [], [], [], []
   obs = None
   for i in range(total):
@@ -276,6 +286,8 @@ def run(env, policies, num_steps=1024, seed=11, keep_values=False, verbose=False
     pixels.append(torch.stack(acts) % A)
     if keep_values:
       kept.append(torch.stack([_chosen_rows(v, a, A).float() for v, a in zip(vals, acts)]))
+    if visualize is not None:
+      visualize(i % num_steps, index, view.frames(*env.render('rgb_array', dtype='uint8'), vals, acts, index, shown))
     obs, r, d = _wait(env.step(acts[index]))
     if r.dim() != 1:
       raise ValueError('run needs one reward per env, got {}'.format(tuple(r.shape)))
@@ -284,6 +296,8 @@ def run(env, policies, num_steps=1024, seed=11, keep_values=False, verbose=False
     if bool(d.any()):                    # the reset call: not a step
       hold = torch.where(d.bool(), torch.zeros_like(acts[index]), torch.full_like(acts[index], HOLD))
       obs = _wait(env.step(hold))[0]
+  if visualize is not None and callable(getattr(visualize, 'close', None)):
+    visualize.close()
   pix = torch.stack(pixels, 1).cpu().numpy()                                  # [P, T, B]
   adt = np.uint8 if max(vshape) < 2 ** 8 else np.uint16
   data = {
@@ -475,18 +489,19 @@ def write(fname, force=False, **kwargs):
 
 # ------------------------------------------------------------------------------------------------ test (test.py:723-919)
 def test(policies, num_steps=1000, seed=11, save=None, verbose=True, show=False, keep_values=False, plots=None, with_env=None,
-         **env_kwargs):
+         visualize=None, **env_kwargs):
   """The command (test.py:723-919, without the curriculum form): make the env from `env_kwargs` (`stackrl_amd.env.make`), `run`,
   `analyse`, update `results.csv` in the env's directory — lines of a run with more steps are kept (`priority=num_steps`) — and
   print the returns.  `save`: the base directory (a string), True for './data/test', None or False for no files.  `plots`
   (default: as `save`) saves the plots with the files, into `<base>/<env path>/<seed>-<num_steps>/`.  `with_env(env, policies)`
-  may return the policies to run once the env exists (policies that need it: `lookahead.LookaheadPolicy`).  Returns the analysis."""
+  may return the policies to run once the env exists (policies that need it: `lookahead.LookaheadPolicy`).  `visualize`: as in
+  `run`.  Returns the analysis."""
   from stackrl_amd import env as envs
   env = envs.make(**env_kwargs)
   try:
     if with_env is not None:
       policies = with_env(env, policies)
-    data = run(env, policies, num_steps=num_steps, seed=seed, keep_values=keep_values, verbose=verbose)
+    data = run(env, policies, num_steps=num_steps, seed=seed, keep_values=keep_values, verbose=verbose, visualize=visualize)
   finally:
     env.close()
   base = os.path.join(save if isinstance(save, str) else os.path.join('data', 'test'),

@@ -5,10 +5,15 @@ and writes `results.csv` (and `data.npz`) under `--save`.
 
   python tools/compare_policies.py [--env Stack-v0] [--envs 16] [--num-steps 64] [--episode-length 8]
                                    [--baselines random,height,difference,corrcoef] [--weights FILE] [--save DIR] [--plots]
-                                   [--lookahead K]
+                                   [--lookahead K] [--visualize DIR [--show 0,1] [--scale 2] [--mark]]
 
 `--lookahead K` adds `<name>+look<K>` beside every policy: of the policy's own action and the K - 1 best other entries of its
 value map, the one whose simulated step gives the highest reward (stackrl_amd/lookahead.py).
+
+`--visualize DIR` writes the picture of the reference's `-v/--visualize` for the envs of `--show` at every step, drawn on the
+device (stackrl_amd/valueview.py): `DIR/policy<p>_step<t>_env<i>.ppm` and `DIR/frames.npy`.  A frame holds the overhead view,
+the object view below it and one tile per policy, the driving policy's framed; frames carry no text, so the order of the tiles is
+printed.  `--mark` also draws each policy's chosen pixel, and the driving policy's window in the overhead view, in red.
 """
 import argparse
 import os
@@ -35,6 +40,10 @@ def main():
   ap.add_argument('--plots', action='store_true')
   ap.add_argument('--keep-values', action='store_true')
   ap.add_argument('--lookahead', type=int, default=0, metavar='K', help='adds <name>+look<K> beside every policy')
+  ap.add_argument('--visualize', default=None, metavar='DIR', help='write the frames of a visualised run under DIR')
+  ap.add_argument('--show', default='0', help='with --visualize: comma-separated env indices whose frames are written')
+  ap.add_argument('--scale', type=int, default=2, help='with --visualize: output pixels per source pixel (1..8)')
+  ap.add_argument('--mark', action='store_true', help='with --visualize: mark the chosen pixels in red')
   args = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit('compare_policies needs a HIP device')
@@ -63,8 +72,22 @@ def main():
       out[name] = p
       out['{}+look{}'.format(name, args.lookahead)] = LookaheadPolicy(p, looks[0])
     return out
+  recorder = None
+  if args.visualize:
+    from stackrl_amd import valueview
+    shown = [int(i) for i in args.show.split(',') if i != '']
+    if not shown or min(shown) < 0 or max(shown) >= args.envs:
+      raise SystemExit('--show must name envs in 0..{}'.format(args.envs - 1))
+    recorder = valueview.Recorder(args.visualize, envs=shown, scale=args.scale, mark=args.mark)
   res = compare.test(policies, num_steps=args.num_steps, seed=args.seed, save=args.save, plots=args.plots,
-                     keep_values=args.keep_values, with_env=with_lookahead if args.lookahead > 0 else None, **env_kwargs)
+                     keep_values=args.keep_values, with_env=with_lookahead if args.lookahead > 0 else None,
+                     visualize=recorder, **env_kwargs)
+  if recorder:
+    names = [str(k) for k in res['keys']]
+    print('frames: {} files under {} ({} x {} pixels); tiles, left to right and line by line, when a policy drives:'.format(
+      len(recorder.frames) * len(recorder.envs) + 1, args.visualize, *recorder.frames[0][2].shape[1:3][::-1]))
+    for i, name in enumerate(names):
+      print('  policy{} {}: {}'.format(i, name, ', '.join('[{}]'.format(n) if n == name else n for n in valueview.tile_order(names, i))))
   for look in looks:
     look.close()
   np.set_printoptions(precision=3, suppress=True, linewidth=160)
