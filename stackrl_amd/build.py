@@ -16,6 +16,7 @@ QLIB = os.path.join(HERE, 'libstackrl_qnet.so')
 CLIB = os.path.join(HERE, 'libstackrl_compare.so')
 RLIB = os.path.join(HERE, 'libstackrl_rocks.so')
 VLIB = os.path.join(HERE, 'libstackrl_valueview.so')
+KLIB = os.path.join(HERE, 'libstackrl_candidates.so')
 _BASE = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared']
 _WARN = ['-Wall', '-Wno-unused-function', '-Wno-unused-value', '-Wno-unused-result']
 # -ffp-contract=off: the solver/rasteriser definition is "one IEEE rounding per written operation"
@@ -155,6 +156,8 @@ ASSET_LIBRARIES = {
   'rocks': _library(RLIB, ['rocks.hip'], QFLAGS, ('no-slp',)),
   # the frames of a visualised comparison run (include/stackrl_valueview.h); tests/test_valueview_abi.py holds its guard
   'valueview': _library(VLIB, ['valueview.hip'], QFLAGS, ('no-slp',)),
+  # the spread candidates of a lookahead (include/stackrl_candidates.h); tests/test_candidates_abi.py holds its guard
+  'candidates': _library(KLIB, ['candidates.hip'], QFLAGS, ('no-slp',)),
 }
 QSRC = LIBRARIES['qnet'].sources
 

@@ -105,15 +105,33 @@ class LookaheadPolicy(object):
   """`(obs, n_valid=None) -> (actions, values)`: of the base policy's action (candidate 0) and the k - 1 best other entries
   of its value map (by value descending, ties to the lower index), the one whose step gives the highest reward (ties to the
   lower candidate rank).  `values` is the base's map; with k = 1 this is the base policy.  `lookahead`: a `Lookahead`, or
-  anything with `k` and `evaluate(actions [B, k]) -> (reward [B, k], done)`."""
+  anything with `k` and `evaluate(actions [B, k]) -> (reward [B, k], done)`.
 
-  def __init__(self, base, lookahead):
+  With an integer `radius` the candidates are spread (stackrl_amd/candidates.py, include/stackrl_candidates.h): every
+  candidate strikes the entries of its map within `radius` pixels, and the next one is the best entry left; `last_count` [B]
+  then says how many distinct candidates an env had (the slots beyond repeat candidate 0).  Radius 0 gives the candidates of
+  `radius=None`, picked by the kernel; k is at most 32 there."""
+
+  def __init__(self, base, lookahead, radius=None):
     self.base, self.lookahead = base, lookahead
+    self.radius = None if radius is None else int(radius)
+    self.last_count = None
+    if self.radius is not None:
+      from stackrl_amd import candidates as _candidates
+      if self.radius < 0:
+        raise ValueError('radius must be at least 0, got {}'.format(radius))
+      if int(lookahead.k) > _candidates.MAX_K:
+        raise ValueError('a radius needs k <= {}, got {}'.format(_candidates.MAX_K, lookahead.k))
 
   def candidates(self, obs, n_valid=None):
     action, values = self.base(obs) if n_valid is None else self.base(obs, n_valid=n_valid)
     action = torch.as_tensor(action)
     values = torch.as_tensor(values, device=action.device)
+    if self.radius is not None:
+      from stackrl_amd import candidates as _candidates
+      cand, self.last_count = _candidates.select(values.reshape(action.shape[0], -1), action, k=self.lookahead.k, radius=self.radius,
+                                                 n_valid=n_valid, OH=int(obs[0].shape[1]) - int(obs[1].shape[-3]) + 1)
+      return cand, values
     n_actions = None
     if n_valid is not None:
       n_actions = values.reshape(action.shape[0], -1).shape[1] // obs[1].shape[1]

@@ -5,10 +5,12 @@ and writes `results.csv` (and `data.npz`) under `--save`.
 
   python tools/compare_policies.py [--env Stack-v0] [--envs 16] [--num-steps 64] [--episode-length 8]
                                    [--baselines random,height,difference,corrcoef] [--weights FILE] [--save DIR] [--plots]
-                                   [--lookahead K] [--visualize DIR [--show 0,1] [--scale 2] [--mark]]
+                                   [--lookahead K [--spread R]] [--visualize DIR [--show 0,1] [--scale 2] [--mark]]
 
 `--lookahead K` adds `<name>+look<K>` beside every policy: of the policy's own action and the K - 1 best other entries of its
-value map, the one whose simulated step gives the highest reward (stackrl_amd/lookahead.py).
+value map, the one whose simulated step gives the highest reward (stackrl_amd/lookahead.py).  With `--spread R` the policies
+are named `<name>+look<K>r<R>` and their candidates are spread: each strikes the entries of its map within R pixels, and the
+next is the best entry left (stackrl_amd/candidates.py).
 
 `--visualize DIR` writes the picture of the reference's `-v/--visualize` for the envs of `--show` at every step, drawn on the
 device (stackrl_amd/valueview.py): `DIR/policy<p>_step<t>_env<i>.ppm` and `DIR/frames.npy`.  A frame holds the overhead view,
@@ -40,11 +42,14 @@ def main():
   ap.add_argument('--plots', action='store_true')
   ap.add_argument('--keep-values', action='store_true')
   ap.add_argument('--lookahead', type=int, default=0, metavar='K', help='adds <name>+look<K> beside every policy')
+  ap.add_argument('--spread', type=int, default=None, metavar='R', help='with --lookahead: spread the candidates by radius R; names <name>+look<K>r<R>')
   ap.add_argument('--visualize', default=None, metavar='DIR', help='write the frames of a visualised run under DIR')
   ap.add_argument('--show', default='0', help='with --visualize: comma-separated env indices whose frames are written')
   ap.add_argument('--scale', type=int, default=2, help='with --visualize: output pixels per source pixel (1..8)')
   ap.add_argument('--mark', action='store_true', help='with --visualize: mark the chosen pixels in red')
   args = ap.parse_args()
+  if args.spread is not None and (args.lookahead < 1 or args.spread < 0):
+    raise SystemExit('--spread needs --lookahead K and a radius of at least 0')
   if not torch.cuda.is_available():
     raise SystemExit('compare_policies needs a HIP device')
   policies = {m: Baseline(m, value=True, seed=3 if m == 'random' else None) for m in args.baselines.split(',') if m}
@@ -70,7 +75,10 @@ def main():
     out = {}
     for name, p in policies.items():
       out[name] = p
-      out['{}+look{}'.format(name, args.lookahead)] = LookaheadPolicy(p, looks[0])
+      if args.spread is None:
+        out['{}+look{}'.format(name, args.lookahead)] = LookaheadPolicy(p, looks[0])
+      else:
+        out['{}+look{}r{}'.format(name, args.lookahead, args.spread)] = LookaheadPolicy(p, looks[0], radius=args.spread)
     return out
   recorder = None
   if args.visualize:
