@@ -229,6 +229,20 @@ class VecStackEnv(object):
     if self._side is not None:
       torch.cuda.current_stream(self._device).wait_stream(self._side)
 
+  def _launch(self, export, *args, tensors=(), join=True):
+    """`export(handle, *args, stream)` on the env's stream: after what the caller has queued (`_fork`), on the env's device, with
+    `tensors` (None entries skipped) kept from the caching allocator while the side stream uses them; then the caller's stream
+    waits for it, unless a `wait` returned later does (`join=False`)."""
+    self._fork()
+    with torch.cuda.device(self._device):
+      _check(getattr(self._lib, export)(self._h, *args, self._stream()))
+    if self._side is not None:
+      for t in tensors:
+        if t is not None:
+          t.record_stream(self._side)
+    if join:
+      self._join()
+
   def _new_obs(self):
     dt = self._observation_spec[0].dtype
     return (torch.empty((self._B, self._H, self._H, 2), dtype=dt, device=self._device),
@@ -244,14 +258,9 @@ class VecStackEnv(object):
   def reset(self, block=None, out=None):
     """out: optional (obs_map, obs_obj) tensors to write into (views of a larger batch, `PipelinedVecStackEnv`)."""
     om, oo = self._new_obs() if out is None else out
-    self._fork()
-    with torch.cuda.device(self._device):
-      _check(self._lib.srl_reset(self._h, om.data_ptr(), oo.data_ptr(), self._stream()))
+    self._launch('srl_reset', om.data_ptr(), oo.data_ptr(), tensors=(om, oo), join=False)
     self._left = self.config.episode_length
     self._needs_reset = self._script_pending = False
-    if self._side is not None:      # the caching allocator must not hand these blocks out again while the side stream writes them
-      for t in (om, oo):
-        t.record_stream(self._side)
     keys = self.config.reward_keys
     out = ((om, oo), torch.zeros(self._B if keys is None else (self._B, len(keys)), dtype=torch.float32, device=self._device),
            torch.zeros(self._B, dtype=torch.bool, device=self._device))     # utils.py:545-552
@@ -275,16 +284,11 @@ class VecStackEnv(object):
       done = torch.empty(self._B, dtype=torch.uint8, device=self._device)
     else:
       om, oo, reward, done = out
-    self._fork()
-    with torch.cuda.device(self._device):
-      _check(self._lib.srl_step(self._h, action.data_ptr(), om.data_ptr(), oo.data_ptr(), reward.data_ptr(),
-                                done.data_ptr(), self._stream()))
+    self._launch('srl_step', action.data_ptr(), om.data_ptr(), oo.data_ptr(), reward.data_ptr(), done.data_ptr(),
+                 tensors=(om, oo, reward, done, action), join=False)
     if self._left == 0 and not self._holds_at_reset:   # the auto-reset of every env has taken the script, as `reset` does
       self._script_pending = False
     self._left = self.config.episode_length if self._left == 0 else self._left - 1   # env.py:235-236: auto-reset
-    if self._side is not None:
-      for t in (om, oo, reward, done, action):
-        t.record_stream(self._side)
     out = ((om, oo), reward, done.view(torch.bool))
     self._last = out
     self._keep = action   # keep the action tensor alive until the kernels consumed it
@@ -295,12 +299,7 @@ class VecStackEnv(object):
   def sample(self):
     """utils.py:534-538: a batch of uniform random actions."""
     a = torch.empty(self._B, dtype=torch.int64, device=self._device)
-    self._fork()
-    with torch.cuda.device(self._device):
-      _check(self._lib.srl_sample(self._h, a.data_ptr(), self._stream()))
-    if self._side is not None:
-      a.record_stream(self._side)
-    self._join()
+    self._launch('srl_sample', a.data_ptr(), tensors=(a,))
     return a
 
   # ---- states as values (stackrl_amd/state.py; csrc/state.hip)
@@ -321,15 +320,8 @@ class VecStackEnv(object):
     words = _state.layout(self.config)[0]
     rec = torch.empty((n, words), dtype=torch.int32, device=self._device)
     seed, counter = ctypes.c_uint32(), ctypes.c_uint32()
-    self._fork()
-    with torch.cuda.device(self._device):
-      _check(self._lib.srl_state_get(self._h, None if idx is None else idx.data_ptr(), n, rec.data_ptr(), ctypes.byref(seed),
-                                     ctypes.byref(counter), self._stream()))
-    if self._side is not None:
-      for t in (rec, idx):
-        if t is not None:
-          t.record_stream(self._side)
-    self._join()
+    self._launch('srl_state_get', None if idx is None else idx.data_ptr(), n, rec.data_ptr(), ctypes.byref(seed),
+                 ctypes.byref(counter), tensors=(rec, idx))
     return rec, int(seed.value), int(counter.value)
 
   def _set_records(self, records, signature, dst=None, src=None):
@@ -337,15 +329,8 @@ class VecStackEnv(object):
     records = records.to(device=self._device, dtype=torch.int32).contiguous()
     d, s = self._index_tensor(dst), self._index_tensor(src)
     n = int(d.numel()) if d is not None else (int(s.numel()) if s is not None else int(records.shape[0]))
-    self._fork()
-    with torch.cuda.device(self._device):
-      _check(self._lib.srl_state_set(self._h, ctypes.c_uint64(int(signature)), None if d is None else d.data_ptr(),
-                                     None if s is None else s.data_ptr(), n, records.data_ptr(), self._stream()))
-    if self._side is not None:
-      for t in (records, d, s):
-        if t is not None:
-          t.record_stream(self._side)
-    self._join()
+    self._launch('srl_state_set', ctypes.c_uint64(int(signature)), None if d is None else d.data_ptr(),
+                 None if s is None else s.data_ptr(), n, records.data_ptr(), tensors=(records, d, s))
 
   def _host_extra(self, idx):
     return {}
@@ -433,7 +418,7 @@ class VecStackEnv(object):
   def step_simulation(self, n=1):
     """`pb.stepSimulation` x n on every env (no placement, no stop criterion, no render)."""
     self._require_reset('step_simulation')
-    _check(self._lib.srl_step_simulation(self._h, int(n), self._stream()))
+    self._launch('srl_step_simulation', int(n))
     _check(self._lib.srl_sync_status(self._h, self._stream()))
 
   def sweeps(self):
@@ -465,9 +450,8 @@ class VecStackEnv(object):
     """O1 on explicit poses: poses f32[B,32,7], mesh_ids i32[B,32], n_bodies i32[B] (device tensors)."""
     if out is None:
       out = torch.empty((self._B, self._H, self._H), dtype=torch.float32, device=self._device)
-    with torch.cuda.device(self._device):
-      _check(self._lib.srl_render_heightmap(self._h, poses.data_ptr(), mesh_ids.data_ptr(), n_bodies.data_ptr(),
-                                            out.data_ptr(), self._stream()))
+    self._launch('srl_render_heightmap', poses.data_ptr(), mesh_ids.data_ptr(), n_bodies.data_ptr(), out.data_ptr(),
+                 tensors=(poses, mesh_ids, n_bodies, out))
     return out
 
   def render(self, mode='rgb_array', dtype=None, out=None):
@@ -489,28 +473,13 @@ class VecStackEnv(object):
     for t, s in zip((rgb0, rgb1), shapes):
       if tuple(t.shape) != s or t.dtype != dt or t.device != self._device or not t.is_contiguous():
         raise ValueError('out must be contiguous {} tensors of shapes {} and {} on {}'.format(dt, shapes[0], shapes[1], self._device))
-    self._fork()
-    with torch.cuda.device(self._device):
-      _check(self._lib.srl_render_rgb(self._h, code, rgb0.data_ptr(), rgb1.data_ptr(), self._stream()))
-    if self._side is not None:
-      for t in (rgb0, rgb1):
-        t.record_stream(self._side)
-    self._join()
+    self._launch('srl_render_rgb', code, rgb0.data_ptr(), rgb1.data_ptr(), tensors=(rgb0, rgb1))
     return rgb0, rgb1
 
   def _camera_call(self, c, scene, rgb, depth, ids):
     """`srl_render_camera` with the struct `c` on the env's stream, with the fork / join of `render`; any tensor may be None."""
-    tensors = [t for t in tuple(scene or ()) + (rgb, depth, ids) if t is not None]
-    ptr = lambda t: None if t is None else t.data_ptr()
-    sp = [ptr(t) for t in scene] if scene is not None else [None] * 4
-    self._fork()
-    with torch.cuda.device(self._device):
-      _check(self._lib.srl_render_camera(self._h, ctypes.byref(c), sp[0], sp[1], sp[2], sp[3], ptr(rgb), ptr(depth), ptr(ids),
-                                         self._stream()))
-    if self._side is not None:
-      for t in tensors:
-        t.record_stream(self._side)
-    self._join()
+    tensors = tuple(scene or (None,) * 4) + (rgb, depth, ids)
+    self._launch('srl_render_camera', ctypes.byref(c), *[None if t is None else t.data_ptr() for t in tensors], tensors=tensors)
 
   def render_camera(self, width=320, height=240, camera=None, rgb=True, depth=False, ids=False, out=None, scene=None):
     """A perspective view of every env's pile, ray cast on the device (`srl_render_camera`, include/stackrl_hip.h holds the
