@@ -28,13 +28,10 @@
 
 #define SRL_RENDER_THREADS 512
 
-// Diagnostic builds only (tools/stamps_render.py; tools/build_ablation_libs.sh for tools/ab_render.py — the outputs of the
-// ablations are wrong by design):
-//   SRL_STAMPS        per-phase wall-clock stamps of thread 0
-//   SRL_ABL_NOSTORE   no H / observation stores     SRL_ABL_NOCAST  no ray cast     SRL_ABL_NOSTAGE  no staging, no ray cast
-//   SRL_ABL_NOGOAL    no goal-rectangle masks       SRL_ABL_NOOBJ   no object observation
-//   SRL_ABL_NOTAIL    no reduction of the partial sums (no reward)
-//   SRL_ABL_EMPTY     the kernel returns at once (launch + event floor)
+// Diagnostic builds only (tools/stamps_render.py):
+//   SRL_STAMPS        per-phase wall-clock stamps of thread 0, taken in render_body between its phases
+// (The ablation switches that compiled one part of the kernel out, and the plain-store form of its output stores, are retired:
+//  tools/experiments/render_ablation_switches.patch puts them back for a measurement.)
 #ifdef SRL_STAMPS
 #define RSTAMP(k) do { if (tid == 0) { long long _t = wall_clock64(); P.hdr[e].rstamps[k] += _t - _t0; _t0 = _t; } } while (0)
 #else
@@ -259,22 +256,14 @@ __device__ __forceinline__ void plane_sweep(const float4* pl, int n, int s, int 
 }
 
 // the kernel's output stores (H float4, packed observation uint2) are non-temporal: the 100 MB a launch writes pass through a
-// 4 MB L2 per XCD once and are read by later kernels only in part (36.0 -> 34.95 us per launch; SRL_PLAIN_STORES: plain ones)
+// 4 MB L2 per XCD once and are read by later kernels only in part (36.0 -> 34.95 us per launch against plain ones)
 typedef float nt_f4 __attribute__((ext_vector_type(4)));
 typedef unsigned int nt_u2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void out_f4(float* base, int g, float4 v) {
-#ifndef SRL_PLAIN_STORES
   __builtin_nontemporal_store((nt_f4){v.x, v.y, v.z, v.w}, (nt_f4*)base + g);
-#else
-  ((float4*)base)[g] = v;
-#endif
 }
 __device__ __forceinline__ void out_u2(uint8_t* base, int g, uint2 v) {
-#ifndef SRL_PLAIN_STORES
   __builtin_nontemporal_store((nt_u2){v.x, v.y}, (nt_u2*)base + g);
-#else
-  ((uint2*)base)[g] = v;
-#endif
 }
 // NT = false: a plain store.  The observation of a 4-pixel group is 32 or 64 bytes for 4- and 8-byte elements, written by
 // 2 or 4 stores of 16 bytes, so that each store instruction of a wave covers only every second (fourth) 16-byte piece of
@@ -283,9 +272,7 @@ __device__ __forceinline__ void out_u2(uint8_t* base, int g, uint2 v) {
 typedef unsigned int nt_u4 __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ void out_u4(uint8_t* base, int g, uint4 v) {
-#ifndef SRL_PLAIN_STORES
   if (NT) { __builtin_nontemporal_store((nt_u4){v.x, v.y, v.z, v.w}, (nt_u4*)base + g); return; }
-#endif
   ((uint4*)base)[g] = v;
 }
 __device__ __forceinline__ uint4 u64_pair(uint64_t a, uint64_t b) {
@@ -401,21 +388,11 @@ extern "C" __global__ void __launch_bounds__(256) srl_k_stage(DevParams P, float
   stage_compute(A, lds[wave], stage + ((size_t)e * slots + b) * SRL_STAGE_STRIDE, xb, q, mh, g, lane);
 }
 
-// poses_ext != nullptr: test/profiling hook rendering explicit poses (srl_render_heightmap)
-// DT: the observation's element type (SRL_DTYPE_*); one kernel per type (srl_k_render = uint8, srl_k_render_u16 ...)
-template <int DT>
-__device__ __forceinline__ void render_body(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* __restrict__ obs_map,
-                                            uint8_t* __restrict__ obs_obj, float* __restrict__ reward, uint8_t* __restrict__ done,
-                                            const int32_t* __restrict__ nb_ext, float* __restrict__ height_ext) {
-  extern __shared__ float4 lds_raw[];
-  constexpr int ES = ObsElem<DT>::size;
-#ifdef SRL_ABL_EMPTY
-  if (P.px != 12345.0f) return;
-#endif
-  const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int res = P.c.overhead_res, npx = res * res;
+// ------------------------------------------------------------------ srl_k_render: the phases of render_body, in the order they run
+// the LDS carve (RenderLds) of a workgroup's dynamic shared memory
+__device__ __forceinline__ RenderLds render_lds(float4* raw, int npx) {
   RenderLds L;
-  L.tile = (float*)lds_raw;
+  L.tile = (float*)raw;
   L.planes = (float4*)(L.tile + npx);
   L.prange = (int*)(L.planes + SRL_PLANE_CAP);
   L.reg = L.prange + 4 * SRL_MAX_BODIES;
@@ -425,14 +402,77 @@ __device__ __forceinline__ void render_body(DevParams P, const float4* __restric
   L.misc = (int*)(L.rowmask + 8);
   L.pi = (float*)L.planes;
   L.pu = L.pi + SRL_RENDER_THREADS;
+  return L;
+}
+
+// What the phases share: written by the prologue, read by the others.  (Pointers first, then 4-byte words only: the compiler
+// fetches a word together with its neighbours where it likes, and a block of mixed sizes it cannot keep in registers.)
+struct RenderCtx {
+  const float4* srec;                        // the env's stage records
+  EnvHdr* h;
+  float* Hout;                               // outputs of this env (om = nullptr with explicit poses)
+  uint8_t* om;
+  float h_empty, gz, nearp;                  // the height of a pixel no rock reaches, the goal height, the near plane
+  uint32_t b_empty;                          // the observation code of a pixel no rock reaches
+  uint32_t gbyte, zbyte, gdiff, zpair;       // goal words: the goal channel's two codes; as bits of a packed uint8 pixel pair
+  int g0, g1, g2, g3;                        // goal rectangle: rows [g0, g0 + g2) x columns [g1, g1 + g3)
+  int e, tid, res, nb;
+  // pixel-group walk of a thread: group g = tid + 512 k holds pixels 4 g .. 4 g + 3 = row i, columns jb .. jb + 3
+  // (res is a multiple of 8); from one round to the next the group advances by di rows and dj columns
+  int walk_i0, walk_j0, walk_di, walk_dj, ngroups4, nrounds;
+  // res divides 4 * 512 (64, 128, 256 ...): the walk never changes columns, so the column part of the goal test is
+  // a per-thread constant: bit t of colmask = column walk_j0 + t lies in the goal rectangle's column range
+  // (maps of fewer than 4 x 512 pixels take the general walk: its rounds test the group index against the map size)
+  uint32_t colmask;
+  bool aligned;
+  bool ext;                                  // explicit poses (srl_render_heightmap): height map only, no observation, no reward
+};
+
+// the words of the episode state the object observation and the reward need, requested in the prologue
+struct EpisodeWords {
+  int pending, left, mode, hdone;
+  float prev_m[4];
+};
+
+// the walk itself: (i, jb) of the thread's group in round 0, step() to the next round's; used by the early stores and the epilogue
+struct GroupWalk {
+  int i, jb, di, dj, res;
+  __device__ __forceinline__ explicit GroupWalk(const RenderCtx& C) : i(C.walk_i0), jb(C.walk_j0), di(C.walk_di), dj(C.walk_dj), res(C.res) {}
+  __device__ __forceinline__ void step() {
+    jb += dj; i += di;
+    if (jb >= res) { jb -= res; ++i; }
+  }
+};
+
+// H and the observation of pixel group g leave: hv = the four heights; the observation is the two packed words w_lo, w_hi in
+// the uint8 kernel and, in the others, made of the pixels' codes hb and their goal bits gm (a kernel never evaluates the other form)
+template <int DT>
+__device__ __forceinline__ void store_group(const RenderCtx& C, int g, const float (&hv)[4], uint32_t w_lo, uint32_t w_hi,
+                                            const uint32_t (&hb)[4], uint32_t gm) {
+  out_f4(C.Hout, g, make_float4(hv[0], hv[1], hv[2], hv[3]));
+  if constexpr (DT == SRL_DTYPE_UINT8) {
+    if (C.om) out_u2(C.om, g, make_uint2(w_lo, w_hi));
+  } else {
+    if (C.om) out_obs<DT>(C.om, g, hb, gm, C.gbyte, C.zbyte);
+  }
+}
+// the same for a group no rock reaches
+template <int DT>
+__device__ __forceinline__ void store_empty_group(const RenderCtx& C, int g, uint32_t w_lo, uint32_t w_hi, uint32_t gm) {
+  store_group<DT>(C, g, {C.h_empty, C.h_empty, C.h_empty, C.h_empty}, w_lo, w_hi, {C.b_empty, C.b_empty, C.b_empty, C.b_empty}, gm);
+}
+
+// ---- prologue.  The record headers of every body slot are requested before the rock count is known (one memory round
+//      trip less); so are the words of the episode state the tail needs: their latency overlaps the ray cast.
+//      Then the region table, the row mask, the span / range tables and the epilogue constants.
+template <int DT>
+__device__ __forceinline__ void render_prologue(const DevParams& P, const RenderLds& L, const float4* __restrict__ stage, int slots,
+                                                uint8_t* __restrict__ obs_map, const int32_t* __restrict__ nb_ext,
+                                                float* __restrict__ height_ext, RenderCtx& C, EpisodeWords& W) {
+  const int e = blockIdx.x, tid = threadIdx.x;
+  const int res = P.c.overhead_res, npx = res * res;
   EnvHdr* h = &P.hdr[e];
-  const float* gb = P.blob + (size_t)e * P.BLOB;
   const bool ext = nb_ext != nullptr;
-#ifdef SRL_STAMPS
-  long long _t0 = wall_clock64();
-#endif
-  // ---- prologue.  The record headers of every body slot are requested before the rock count is known (one memory round
-  //      trip less); so are the words of the episode state the tail needs: their latency overlaps the ray cast.
   const float4* srec = stage + (size_t)e * slots * SRL_STAGE_STRIDE;
   int4 hd0 = make_int4(0, -65536, 0, 0), hd1 = make_int4(0, 0, 0, 0);
   if (tid < slots) {
@@ -441,17 +481,18 @@ __device__ __forceinline__ void render_body(DevParams P, const float4* __restric
     hd1 = make_int4(__float_as_int(c.x), __float_as_int(c.y), __float_as_int(c.z), __float_as_int(c.w));
   }
   const int nb = ext ? nb_ext[e] : h->nb;
-  int g0 = 0, g1 = 0, g2 = 0, g3 = 0, pending = -1, mode = 0, hdone = 0, left = 0;
-  float prev_m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (!ext) {
-    g0 = h->goal[0]; g1 = h->goal[1]; g2 = h->goal[2]; g3 = h->goal[3]; pending = h->pending;
-    mode = h->mode; hdone = h->done; left = h->list_pos;
+  int g0 = 0, g1 = 0, g2 = 0, g3 = 0;
+  W.pending = -1; W.mode = 0; W.hdone = 0; W.left = 0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) prev_m[k] = h->prev_metric[k];
+  for (int k = 0; k < 4; ++k) W.prev_m[k] = 0.0f;
+  if (!ext) {
+    g0 = h->goal[0]; g1 = h->goal[1]; g2 = h->goal[2]; g3 = h->goal[3]; W.pending = h->pending;
+    W.mode = h->mode; W.hdone = h->done; W.left = h->list_pos;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) W.prev_m[k] = h->prev_metric[k];
   }
-  const int rr = P.c.object_res * P.c.object_res * P.n_orient;   // all observable orientations of the pending rock
-  // (the tile is zeroed where a rock may write — the groups of the rows some bounding box reaches — in the early-store loop
-  //  below, whose thread-to-group map the epilogue shares; a block barrier lies between that loop and the ray cast)
+  // (the tile is zeroed where a rock may write — the groups of the rows some bounding box reaches — in the early-store loop,
+  //  whose thread-to-group map the epilogue shares; a block barrier lies between that loop and the ray cast)
   if (tid < 8) L.rowmask[tid] = 0u;                  // (wave 0, like the atomicOr below: LDS keeps a wave's order)
   if (tid < SRL_MAX_BODIES) {
     // a rock's region holds its up-facing planes and the sides of its outline (a rock outside the window has neither)
@@ -480,372 +521,351 @@ __device__ __forceinline__ void render_body(DevParams P, const float4* __restric
     if (k < 4) ((float4*)L.span)[4 * b + k] = v; else ((float4*)L.range)[4 * b + k - 4] = v;
   }
   // epilogue constants
-  const float nearp = SRL_FAR - P.c.max_z;
-  const float gz = P.goal_z;
-  const uint32_t gbyte = P.gbyte, zbyte = P.zbyte, b_empty = P.b_empty;   // (DevParams: evaluated once on the device)
-  const float h_empty = P.h_empty;
-  float* Hout = ext ? height_ext + (size_t)e * npx : P.H + (size_t)e * npx;
-  uint8_t* om = ext ? nullptr : obs_map + (size_t)e * npx * 2 * ES;
-  const int ngroups4 = npx / 4, nrounds = (ngroups4 + SRL_RENDER_THREADS - 1) / SRL_RENDER_THREADS;
-  // pixel-group walk of a thread: group g = tid + 512 k holds pixels 4 g .. 4 g + 3 = row i, columns jb .. jb + 3
-  // (res is a multiple of 8); from one round to the next the group advances by di rows and dj columns
-  const int walk_di = P.walk_di, walk_dj = P.walk_dj;
-  const int walk_i0 = (int)__umulhi((uint32_t)(4 * tid), P.res_magic), walk_j0 = 4 * tid - walk_i0 * res;
-  // res divides 4 * 512 (64, 128, 256 ...): the walk never changes columns, so the column part of the goal test is
-  // a per-thread constant: bit t of colmask = column walk_j0 + t lies in the goal rectangle's column range
-  // (maps of fewer than 4 x 512 pixels take the general walk: its rounds test the group index against the map size)
-  const bool aligned = walk_dj == 0 && ngroups4 >= SRL_RENDER_THREADS;
-  uint32_t colmask = 0u;
-  const uint32_t gdiff = (gbyte ^ zbyte) << 8, zpair = (zbyte << 8) | (zbyte << 24);
-  {
-    const int lo = max(g1 - walk_j0, 0), hi = min(g1 + g3 - walk_j0, 4);
-    colmask = hi > lo ? (1u << hi) - (1u << lo) : 0u;
-  }
-  // ---- object observation (O2 from the per-mesh cache; empty map when nothing is pending): its inputs are known here,
-  //      so it leaves now and drains under everything else
-#ifndef SRL_ABL_NOOBJ
-  if (!ext) {
-    // the pending rock's maps, or with ordering freedom (observer.py:310-327) those of the rocks still unplaced, in list
-    // order, then empty maps; bytes from the per-mesh cache, four pixels per lane (the map size is a multiple of 4)
-    const int shown = P.c.ordering_freedom ? P.c.episode_length : 1;
-    if constexpr (DT == SRL_DTYPE_UINT8) {
-      uint32_t* oo = (uint32_t*)(obs_obj + (size_t)e * rr * shown);
-      const uint32_t eb4 = P.obj_empty_byte * 0x01010101u;
-      for (int k = 0; k < shown; ++k) {
-        const int m = P.c.ordering_freedom ? (k < left ? h->ids[k] : -1) : pending;
-        const uint32_t* src = (const uint32_t*)(P.objmap_u8 + (size_t)(m < 0 ? 0 : m) * rr);
-        for (int idx = tid; idx < rr / 4; idx += SRL_RENDER_THREADS) oo[(size_t)k * (rr / 4) + idx] = m >= 0 ? src[idx] : eb4;
-      }
-    } else {
-      // other types: codes of the float cache's values (no cache per type), the empty map's code from DevParams
-      uint8_t* oo = obs_obj + (size_t)e * rr * shown * ES;
-      const float den = fmaxf(P.c.max_z, P.c.object_max_dimension);
-      const uint32_t ec = P.obj_empty_byte;
-      for (int k = 0; k < shown; ++k) {
-        const int m = P.c.ordering_freedom ? (k < left ? h->ids[k] : -1) : pending;
-        const float4* src = (const float4*)(P.objmap + (size_t)(m < 0 ? 0 : m) * rr);
-        for (int idx = tid; idx < rr / 4; idx += SRL_RENDER_THREADS) {
-          uint32_t c[4] = {ec, ec, ec, ec};
-          if (m >= 0) {
-            const float4 v = src[idx];
-            c[0] = obs_code(DT, v.x, den); c[1] = obs_code(DT, v.y, den); c[2] = obs_code(DT, v.z, den); c[3] = obs_code(DT, v.w, den);
-          }
-          out_obj<DT>(oo, (size_t)k * (rr / 4) + idx, c);
+  C.e = e; C.tid = tid; C.res = res; C.nb = nb; C.ext = ext; C.srec = srec; C.h = h;
+  C.g0 = g0; C.g1 = g1; C.g2 = g2; C.g3 = g3;
+  C.nearp = SRL_FAR - P.c.max_z;
+  C.gz = P.goal_z;
+  C.gbyte = P.gbyte; C.zbyte = P.zbyte; C.b_empty = P.b_empty;   // (DevParams: evaluated once on the device)
+  C.h_empty = P.h_empty;
+  C.Hout = ext ? height_ext + (size_t)e * npx : P.H + (size_t)e * npx;
+  C.om = ext ? nullptr : obs_map + (size_t)e * npx * 2 * ObsElem<DT>::size;
+  C.ngroups4 = npx / 4; C.nrounds = (C.ngroups4 + SRL_RENDER_THREADS - 1) / SRL_RENDER_THREADS;
+  C.walk_di = P.walk_di; C.walk_dj = P.walk_dj;
+  C.walk_i0 = (int)__umulhi((uint32_t)(4 * tid), P.res_magic); C.walk_j0 = 4 * tid - C.walk_i0 * res;
+  C.aligned = C.walk_dj == 0 && C.ngroups4 >= SRL_RENDER_THREADS;
+  C.gdiff = (C.gbyte ^ C.zbyte) << 8; C.zpair = (C.zbyte << 8) | (C.zbyte << 24);
+  const int lo = max(g1 - C.walk_j0, 0), hi = min(g1 + g3 - C.walk_j0, 4);
+  C.colmask = hi > lo ? (1u << hi) - (1u << lo) : 0u;
+}
+
+// the mesh on show in slot k of the object observation: the pending rock's, or with ordering freedom (observer.py:310-327)
+// that of the k-th rock still unplaced, in list order; -1 = an empty map
+__device__ __forceinline__ int mesh_on_show(const DevParams& P, const RenderCtx& C, const EpisodeWords& W, int k) {
+  return P.c.ordering_freedom ? (k < W.left ? C.h->ids[k] : -1) : W.pending;
+}
+
+// ---- object observation (O2 from the per-mesh cache; empty map when nothing is pending): its inputs are known after the
+//      prologue, so it leaves then and drains under everything else
+template <int DT>
+__device__ __forceinline__ void object_observation(const DevParams& P, const RenderCtx& C, const EpisodeWords& W, uint8_t* __restrict__ obs_obj) {
+  // the maps of the meshes on show, bytes from the per-mesh cache, four pixels per lane (the map size is a multiple of 4)
+  const int rr = P.c.object_res * P.c.object_res * P.n_orient;   // all observable orientations of a rock
+  const int shown = P.c.ordering_freedom ? P.c.episode_length : 1;
+  if constexpr (DT == SRL_DTYPE_UINT8) {
+    uint32_t* oo = (uint32_t*)(obs_obj + (size_t)C.e * rr * shown);
+    const uint32_t eb4 = P.obj_empty_byte * 0x01010101u;
+    for (int k = 0; k < shown; ++k) {
+      const int m = mesh_on_show(P, C, W, k);
+      const uint32_t* src = (const uint32_t*)(P.objmap_u8 + (size_t)(m < 0 ? 0 : m) * rr);
+      for (int idx = C.tid; idx < rr / 4; idx += SRL_RENDER_THREADS) oo[(size_t)k * (rr / 4) + idx] = m >= 0 ? src[idx] : eb4;
+    }
+  } else {
+    // other types: codes of the float cache's values (no cache per type), the empty map's code from DevParams
+    uint8_t* oo = obs_obj + (size_t)C.e * rr * shown * ObsElem<DT>::size;
+    const float den = fmaxf(P.c.max_z, P.c.object_max_dimension);
+    const uint32_t ec = P.obj_empty_byte;
+    for (int k = 0; k < shown; ++k) {
+      const int m = mesh_on_show(P, C, W, k);
+      const float4* src = (const float4*)(P.objmap + (size_t)(m < 0 ? 0 : m) * rr);
+      for (int idx = C.tid; idx < rr / 4; idx += SRL_RENDER_THREADS) {
+        uint32_t c[4] = {ec, ec, ec, ec};
+        if (m >= 0) {
+          const float4 v = src[idx];
+          c[0] = obs_code(DT, v.x, den); c[1] = obs_code(DT, v.y, den); c[2] = obs_code(DT, v.z, den); c[3] = obs_code(DT, v.w, den);
         }
+        out_obj<DT>(oo, (size_t)k * (rr / 4) + idx, c);
       }
     }
   }
-#endif
-  __syncthreads();
-  RSTAMP(0);
-  // ---- groups of rocks whose planes fit the staging area
-  int bs = 0, be = L.misc[0];   // (be >= 1 when nb >= 1: a mesh has at most SRL_MAX_TRIS + 2 <= SRL_PLANE_CAP slots)
+}
+
+// ---- staging of a rock group [bs, be): its planes and outline sides from their records (srl_k_stage) into the regions, the
+//      rocks handed to the 8 waves round robin, lanes over a rock's slots.  The first 64 slots of a wave's first rock are
+//      requested by stage_first (on the first trip their latency hides under the early stores) and written to LDS, with the
+//      rest, by stage_group.  (Requesting them two barriers earlier, from the prologue, was measured: no gain.)
+struct StageFirst {
+  int pb, pbase, pcnt;   // the wave's first rock, its region base and slot count (0: the wave has none)
+  float4 pv;
+};
+__device__ __forceinline__ StageFirst stage_first(const RenderCtx& C, const RenderLds& L, int bs, int be) {
+  const int lane = C.tid & 63, wave = C.tid >> 6;
+  StageFirst F;
+  F.pb = bs + wave;
+  F.pbase = 0; F.pcnt = 0;
+  if (F.pb < be) { F.pbase = L.reg[4 * F.pb + 0]; F.pcnt = L.reg[4 * F.pb + 1] + L.reg[4 * F.pb + 2]; }
+  F.pv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (lane < F.pcnt) F.pv = C.srec[(size_t)F.pb * SRL_STAGE_STRIDE + SRL_STAGE_HDR + lane];
+  return F;
+}
+__device__ __forceinline__ void stage_group(const RenderCtx& C, const RenderLds& L, const StageFirst& F, int be) {
+  const int lane = C.tid & 63;
+  if (lane < F.pcnt) L.planes[F.pbase + lane] = F.pv;
+  for (int b = F.pb; b < be; b += SRL_RENDER_THREADS / 64) {
+    const int base = L.reg[4 * b + 0], cnt = L.reg[4 * b + 1] + L.reg[4 * b + 2];
+    const float4* src = C.srec + (size_t)b * SRL_STAGE_STRIDE + SRL_STAGE_HDR;
+    for (int k = (b == F.pb ? 64 : 0) + lane; k < cnt; k += 64) L.planes[base + k] = src[k];
+  }
+}
+
+// ---- early stores (first trip): rows no rock reaches hold the empty-pixel constants; their H / observation bytes leave
+//      before the ray cast, so that HBM drains them while it computes.  cov bit k: this thread's k-th pixel group lies in
+//      a row some rock may reach (zeroed in the tile here, written by the epilogue); goalm bit k: it touches the goal rectangle.
+__device__ __forceinline__ void claim_group(const RenderLds& L, int g, int k, uint32_t& cov) {
+  cov |= 1u << k; ((float4*)L.tile)[g] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+struct GroupBits { uint32_t cov, goalm; };
+template <int DT>
+__device__ __forceinline__ GroupBits early_stores(const RenderCtx& C, const RenderLds& L) {
   uint32_t cov = 0u, goalm = 0u;
-  bool first = true;
-  do {
-    // (a) the group's planes and outline sides from their records (srl_k_stage) into the regions, the rocks handed to the
-    //     8 waves round robin, lanes over a rock's slots: the first 64 slots of a wave's first rock are requested now and
-    //     written to LDS after the early stores below (their latency hides under those), the rest follows there.
-    //     (Requesting them two barriers earlier, from the prologue, was measured: no gain.)
-    const int pb = bs + wave;
-    int pbase = 0, pcnt = 0;
-    if (pb < be) { pbase = L.reg[4 * pb + 0]; pcnt = L.reg[4 * pb + 1] + L.reg[4 * pb + 2]; }
-    float4 pv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#ifdef SRL_ABL_NOSTAGE
-    if (P.px == 12345.0f)
-#endif
-    if (lane < pcnt) pv = srec[(size_t)pb * SRL_STAGE_STRIDE + SRL_STAGE_HDR + lane];
-    RSTAMP(1);
-    // (d) first trip: rows no rock reaches hold the empty-pixel constants; their H / observation bytes leave
-    //     now, so that HBM drains them while the ray cast computes.  cov bit k: this thread's k-th pixel group
-    //     lies in a row some rock may reach (written by the epilogue).
-    if (first) {
-      const float4 he4 = make_float4(h_empty, h_empty, h_empty, h_empty);
-      const uint32_t epair = b_empty | (b_empty << 16);
-      if (aligned) {
-        // every round keeps the thread's four columns and moves walk_di rows down: the column part of the goal test
-        // and the two possible observation words are fixed, a round costs a row test and a row-mask bit (the mask's four
-        // words — res <= 128 on this path — are read once)
-        const uint4 rm4 = *(const uint4*)L.rowmask;
-        const unsigned long long rlo = rm4.x | ((unsigned long long)rm4.y << 32), rhi = rm4.z | ((unsigned long long)rm4.w << 32);
-        const uint32_t w_out = epair | zpair, w_in_lo = w_out ^ goal_pair(colmask, gdiff), w_in_hi = w_out ^ goal_pair(colmask >> 2, gdiff);
-        for (int k = 0; k < nrounds; ++k) {
-          const int g = tid + k * SRL_RENDER_THREADS, i = walk_i0 + k * walk_di;
-          const bool rowin = (unsigned)(i - g0) < (unsigned)g2;
-#ifndef SRL_ABL_NOGOAL
-          if (rowin && colmask) goalm |= 1u << k;
-#endif
-          if (((i < 64 ? rlo : rhi) >> (i & 63)) & 1ull) { cov |= 1u << k; ((float4*)L.tile)[g] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
-          else {
-#ifndef SRL_ABL_NOSTORE
-            out_f4(Hout, g, he4);
-            if constexpr (DT == SRL_DTYPE_UINT8) {
-              if (om) out_u2(om, g, make_uint2(rowin ? w_in_lo : w_out, rowin ? w_in_hi : w_out));
-            } else {
-              if (om) out_obs<DT>(om, g, {b_empty, b_empty, b_empty, b_empty}, rowin ? colmask : 0u, gbyte, zbyte);
-            }
-#endif
-          }
-        }
-      } else {
-      int i = walk_i0, jb = walk_j0;
-      for (int k = 0; k < nrounds; ++k) {
-        const int g = tid + k * SRL_RENDER_THREADS;
-        if (g >= ngroups4) break;
-        // groups that touch the goal rectangle: their empty pixels still add the goal height to the union sum
-#ifndef SRL_ABL_NOGOAL
-        const uint32_t inm = goal_mask4(i, jb, g0, g2, g1, g3);
-#else
-        const uint32_t inm = 0u;
-#endif
-        if (inm) goalm |= 1u << k;
-        if ((L.rowmask[i >> 5] >> (i & 31)) & 1u) { cov |= 1u << k; ((float4*)L.tile)[g] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
-        else {
-#ifndef SRL_ABL_NOSTORE
-          out_f4(Hout, g, he4);
-          if constexpr (DT == SRL_DTYPE_UINT8) {
-            if (om) out_u2(om, g, make_uint2((epair | zpair) ^ goal_pair(inm, gdiff), (epair | zpair) ^ goal_pair(inm >> 2, gdiff)));
-          } else {
-            if (om) out_obs<DT>(om, g, {b_empty, b_empty, b_empty, b_empty}, inm, gbyte, zbyte);
-          }
-#endif
-        }
-        jb += walk_dj; i += walk_di;
-        if (jb >= res) { jb -= res; ++i; }
-      }
-      }
-      RSTAMP(2);
+  const int tid = C.tid, nrounds = C.nrounds, g0 = C.g0, g2 = C.g2;
+  const uint32_t colmask = C.colmask, gdiff = C.gdiff, zpair = C.zpair;
+  const uint32_t epair = C.b_empty | (C.b_empty << 16);
+  if (C.aligned) {
+    // every round keeps the thread's four columns and moves walk_di rows down: the column part of the goal test
+    // and the two possible observation words are fixed, a round costs a row test and a row-mask bit (the mask's four
+    // words — res <= 128 on this path — are read once)
+    const uint4 rm4 = *(const uint4*)L.rowmask;
+    const unsigned long long rlo = rm4.x | ((unsigned long long)rm4.y << 32), rhi = rm4.z | ((unsigned long long)rm4.w << 32);
+    const uint32_t w_out = epair | zpair, w_in_lo = w_out ^ goal_pair(colmask, gdiff), w_in_hi = w_out ^ goal_pair(colmask >> 2, gdiff);
+    const int walk_i0 = C.walk_i0, walk_di = C.walk_di;
+    for (int k = 0; k < nrounds; ++k) {
+      const int g = tid + k * SRL_RENDER_THREADS, i = walk_i0 + k * walk_di;
+      const bool rowin = (unsigned)(i - g0) < (unsigned)g2;
+      if (rowin && colmask) goalm |= 1u << k;
+      if (((i < 64 ? rlo : rhi) >> (i & 63)) & 1ull) claim_group(L, g, k, cov);
+      else store_empty_group<DT>(C, g, rowin ? w_in_lo : w_out, rowin ? w_in_hi : w_out, rowin ? colmask : 0u);
     }
-    // the group's slots into their regions
-#ifdef SRL_ABL_NOSTAGE
-    if (P.px == 12345.0f)
-#endif
-    {
-      if (lane < pcnt) L.planes[pbase + lane] = pv;
-      for (int b = pb; b < be; b += SRL_RENDER_THREADS / 64) {
-        const int base = L.reg[4 * b + 0], cnt = L.reg[4 * b + 1] + L.reg[4 * b + 2];
-        const float4* src = srec + (size_t)b * SRL_STAGE_STRIDE + SRL_STAGE_HDR;
-        for (int k = (b == pb ? 64 : 0) + lane; k < cnt; k += 64) L.planes[base + k] = src[k];
-      }
-    }
-    __syncthreads();
-    // (e) ray cast: lanes over the flattened (rock, item of SRL_ITEM_ROWS x 2 pixels) list; when the list is short each item
-    //     is shared by S adjacent lanes that split the planes and combine with shuffles
-#ifdef SRL_ABL_NOCAST
-    if (be > bs && P.px == 12345.0f) {
-#else
-    if (be > bs) {
-#endif
-      // item counts of the group's rocks as running sums (registers, one LDS round trip); groups of more
-      // than 8 rocks fall back to walking the list
-      const bool few = be - bs <= 8;
-      int pre[8];
-      int total = 0;
-      if (few) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) pre[r] = bs + r < be ? L.prange[4 * (bs + r) + 3] : 0;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) { total += pre[r]; pre[r] = total; }
-      } else {
-        for (int b = bs; b < be; ++b) total += L.prange[4 * b + 3];
-      }
-      int lg = 0;
-      while (lg < 3 && (total << (lg + 1)) <= SRL_RENDER_THREADS) ++lg;
-      const int S = 1 << lg, s = tid & (S - 1);
-      int wb = bs, wis = 0, wnib = few ? 0 : L.prange[4 * bs + 3];
-      for (int it = tid >> lg; it < total; it += SRL_RENDER_THREADS >> lg) {
-        int b, is;
-        if (few) {
-          b = bs; is = 0;
-#pragma unroll
-          for (int r = 0; r < 7; ++r) if (it >= pre[r]) { b = bs + r + 1; is = pre[r]; }
-        } else {
-          while (it >= wis + wnib) { wis += wnib; ++wb; wnib = L.prange[4 * wb + 3]; }
-          b = wb; is = wis;
-        }
-        const int4 pr = ((const int4*)L.prange)[b], rg = ((const int4*)L.reg)[b];
-        const int nir = pr.z, jj = pr.y, ii = pr.x;
-        const int j0 = jj & 0xffff, j1 = jj >> 16, i1 = ii >> 16;
-        const int p = it - is;
-        int di, j;
-        if (nir > 0) {
-          // item row = the last one whose first item is <= p (rows the outline does not reach share their successor's first
-          // item, rows past the last start at the rock's item count); the row's first column is in the low byte
-          const int4* sp = (const int4*)(L.span + SRL_STAGE_SPANS * b);
-          const int4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
-          const int sv[SRL_STAGE_SPANS] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w, s3.x, s3.y, s3.z, s3.w};
-          const int key = (p << 8) | 0xff;
-          int w = sv[0];
-          di = 0;
-#pragma unroll
-          for (int r = 1; r < SRL_STAGE_SPANS; ++r) if (key >= sv[r]) { w = sv[r]; di = r; }
-          j = (w & 0xff) + 2 * (p - (w >> 8));
-        } else {
-          // items fill the bounding box.  p / w2 without the integer-division sequence: (p + 0.5) / w2 stays at least
-          // 0.5 / w2 >= 1 / 256 away from an integer, far more than the error of the reciprocal (p < 2^14, w2 <= 128)
-          const int w2 = (j1 - j0 + 2) >> 1;
-          di = (int)(((float)p + 0.5f) * __builtin_amdgcn_rcpf((float)w2));
-          j = j0 + 2 * (p - di * w2);
-        }
-        const int i = (ii & 0xffff) + SRL_ITEM_ROWS * di;
-        const bool col2 = j + 1 <= j1;
-        const f32x2 py = {((float)j + 0.5f) * P.px, ((float)(j + 1) + 0.5f) * P.px};
-        f32x2 vx[SRL_ITEM_ROWS], hh[SRL_ITEM_ROWS], ll[SRL_ITEM_ROWS];
-#pragma unroll
-        for (int r = 0; r < SRL_ITEM_ROWS; ++r) {
-          const float x = ((float)(i + r) + 0.5f) * P.px;
-          vx[r].x = x; vx[r].y = x; hh[r].x = 1e30f; hh[r].y = 1e30f; ll[r].x = 1e30f; ll[r].y = 1e30f;
-        }
-        // z_hi = min over the up-facing planes; inside the outline iff the smallest side function is >= 0
-        // the item row's ranges of the two lists (srl_k_stage): the faces / outline edges whose x extent reaches the row
-        const uint32_t rw = nir > 0 ? (uint32_t)L.range[SRL_STAGE_SPANS * b + di] : ((uint32_t)rg.y << 8) | ((uint32_t)rg.z << 24);
-        const int plo = rw & 0xff, pn = ((rw >> 8) & 0xff) - plo, slo = (rw >> 16) & 0xff, sn = (int)(rw >> 24) - slo;
-        plane_sweep<true>(L.planes + rg.x + plo, pn, s, S, py, vx, hh);
-        plane_sweep<true>(L.planes + rg.x + rg.y + slo, sn, s, S, py, vx, ll);
-        const bool lists = pn > 0 && sn > 0;           // (a row the lists do not reach holds no rock pixel)
-        // the S lanes of an item (adjacent, aligned) combine their partial minima with DPP moves folded into the min:
-        // within quads (lanes ^ 1, ^ 2), then across the two quads of a half row (mirror) — no LDS traffic
-        if (S >= 2) {
-#pragma unroll
-          for (int r = 0; r < SRL_ITEM_ROWS; ++r) {
-            hh[r].x = dpp_min<0xB1>(hh[r].x); hh[r].y = dpp_min<0xB1>(hh[r].y);
-            ll[r].x = dpp_min<0xB1>(ll[r].x); ll[r].y = dpp_min<0xB1>(ll[r].y);
-          }
-        }
-        if (S >= 4) {
-#pragma unroll
-          for (int r = 0; r < SRL_ITEM_ROWS; ++r) {
-            hh[r].x = dpp_min<0x4E>(hh[r].x); hh[r].y = dpp_min<0x4E>(hh[r].y);
-            ll[r].x = dpp_min<0x4E>(ll[r].x); ll[r].y = dpp_min<0x4E>(ll[r].y);
-          }
-        }
-        if (S >= 8) {
-#pragma unroll
-          for (int r = 0; r < SRL_ITEM_ROWS; ++r) {
-            hh[r].x = dpp_min<0x141>(hh[r].x); hh[r].y = dpp_min<0x141>(hh[r].y);
-            ll[r].x = dpp_min<0x141>(ll[r].x); ll[r].y = dpp_min<0x141>(ll[r].y);
-          }
-        }
-        if (s == 0) {
-          // the tile holds codec-table rows, not heights: row(z) = codec_n - index of t = fl(FAR - z) is monotone in z,
-          // so the max over rocks commutes with the look-up and the epilogue needs no arithmetic per pixel (0 = no rock)
-          int* t0p = (int*)&L.tile[i * res + j];
-#pragma unroll
-          for (int r = 0; r < SRL_ITEM_ROWS; ++r) {
-            const bool rowok = i + r <= i1;
-            if (lists && rowok && ll[r].x >= 0.0f && hh[r].x > 0.0f) atomicMax(t0p + r * res, codec_row(hh[r].x, nearp, P.codec_n));
-            if (lists && rowok && col2 && ll[r].y >= 0.0f && hh[r].y > 0.0f) atomicMax(t0p + r * res + 1, codec_row(hh[r].y, nearp, P.codec_n));
-          }
-        }
-      }
-    }
-    __syncthreads();
-    RSTAMP(3);
-    first = false;
-    bs = be;
-    if (bs < nb) {   // next group: its extent, then its region cursors
-      const int p0 = L.reg[4 * bs + 3];
-      while (be < nb && L.reg[4 * be + 3] + L.reg[4 * be + 1] + L.reg[4 * be + 2] - p0 <= SRL_PLANE_CAP) ++be;
-      __syncthreads();                               // (every thread has read the old cursors)
-      if (tid >= bs && tid < be) L.reg[4 * tid + 0] = L.reg[4 * tid + 3] - p0;
-      __syncthreads();
-    }
-  } while (bs < nb);
-  RSTAMP(4);
-  // ---- epilogue: depth codec, H out, uint8 pack, IoU partial sums (4 pixels per thread per round, fixed order).
-  //      The kernel is bound by VALU issue, so the pass is branch-free per pixel: the codec is one 8-byte look-up
-  //      (DevParams::codec; a pixel without a rock reads the table's last entry, the empty-pixel constants), the goal
-  //      terms are selected with bit masks.
-  float spi = 0.0f, spu = 0.0f;
-  {
-    // An empty pixel outside the goal adds max(h_empty, 0) to the union sum and nothing else; when that is +0 (it is
-    // whenever FAR (FAR - max_z) is a float32, e.g. the default geometry) the addition is the identity, bit for bit
-    // (the partial sums never hold -0), so rounds whose group lies in a row no rock reaches and outside the goal
-    // rectangle are skipped altogether.  todo bit k: round k must be visited.
-    const uint32_t todo = fmaxf(h_empty, 0.0f) == 0.0f ? (cov | goalm) : 0xffffffffu;
-    const uint2* __restrict__ ctab = P.codec;
-    const uint32_t gp_lo = goal_pair(colmask, gdiff), gp_hi = goal_pair(colmask >> 2, gdiff);
-    // what the four pixels of a group no rock reaches add to the two sums in a goal row (the columns are fixed per
-    // thread when `aligned`): the very terms the general path below computes from the table's empty-pixel entry
-    float cu_in[4], ci_in[4];
-    const float cu_out = fmaxf(h_empty, 0.0f);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int m = __builtin_amdgcn_sbfe((int)colmask, t, 1);
-      cu_in[t] = fmaxf(h_empty, __int_as_float(__float_as_int(gz) & m));
-      ci_in[t] = __int_as_float(__float_as_int(fminf(h_empty, gz)) & m);
-    }
-    int i = walk_i0, jb = walk_j0;
+  } else {
+    const int ngroups4 = C.ngroups4, g1 = C.g1, g3 = C.g3;
+    GroupWalk w(C);
     for (int k = 0; k < nrounds; ++k) {
       const int g = tid + k * SRL_RENDER_THREADS;
-      if (((todo >> k) & 1u) && g < ngroups4) {
-        const bool covg = (cov >> k) & 1u;
-        if (aligned && __builtin_amdgcn_ballot_w64(covg) == 0ull) {
-          // no group of the wave holds a rock pixel this round (their H / observation bytes left with the early stores):
-          // the sums take per-thread constants — no table look-ups, no stores
-          const bool rowin = (unsigned)(i - g0) < (unsigned)g2;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) { spu += rowin ? cu_in[t] : cu_out; spi += rowin ? ci_in[t] : 0.0f; }
-          jb += walk_dj; i += walk_di;
-          if (jb >= res) { jb -= res; ++i; }
-          continue;
-        }
-        uint4 r4 = make_uint4(0u, 0u, 0u, 0u);   // codec-table rows of the four pixels (0: no rock)
-        if (covg) r4 = ((const uint4*)L.tile)[g];
-        const uint32_t rw[4] = {r4.x, r4.y, r4.z, r4.w};
-        float hv[4]; uint32_t hb[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const uint2 en = *(const uint2*)((const char*)ctab + (rw[t] << 3));   // 32-bit offset from a uniform base
-          hv[t] = __uint_as_float(en.x); hb[t] = en.y;
-        }
-        // rewarder.py:297-307: goal pixels add min / max(h, goal) to the two sums, the others max(h, 0) to the union
-        // only (x + 0 = x bit for bit here: the partial sums never hold -0); m = all ones on a goal pixel
-        uint32_t glo = 0u, ghi = 0u;   // goal-channel bits of the two observation words
-        uint32_t gm = 0u;              // (other types: bit t = pixel t lies in the goal rectangle)
-        const bool rowin = (unsigned)(i - g0) < (unsigned)g2;
-        if (aligned && __builtin_amdgcn_ballot_w64(rowin && colmask != 0u) == 0ull) {
-          // none of the wave's groups of this round touches the goal (a wave covers whole rows): union sum only
-#pragma unroll
-          for (int t = 0; t < 4; ++t) spu += fmaxf(hv[t], 0.0f);
-        } else {
-          const uint32_t inm = aligned ? (rowin ? colmask : 0u) : goal_mask4(i, jb, g0, g2, g1, g3);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const int m = __builtin_amdgcn_sbfe((int)inm, t, 1);
-            spu += fmaxf(hv[t], __int_as_float(__float_as_int(gz) & m));
-            spi += __int_as_float(__float_as_int(fminf(hv[t], gz)) & m);
-          }
-          if (aligned) { glo = rowin ? gp_lo : 0u; ghi = rowin ? gp_hi : 0u; }
-          else { glo = goal_pair(inm, gdiff); ghi = goal_pair(inm >> 2, gdiff); }
-          gm = inm;
-        }
-#ifndef SRL_ABL_NOSTORE
-        if (covg) {
-          out_f4(Hout, g, make_float4(hv[0], hv[1], hv[2], hv[3]));
-          if constexpr (DT == SRL_DTYPE_UINT8) {
-            if (om) out_u2(om, g, make_uint2((hb[0] | (hb[1] << 16) | zpair) ^ glo, (hb[2] | (hb[3] << 16) | zpair) ^ ghi));
-          } else {
-            if (om) out_obs<DT>(om, g, hb, gm, gbyte, zbyte);
-          }
-        }
-#else
-        if (covg && hv[0] == 12345.0f && hb[0] == 77u) ((float4*)Hout)[g] = make_float4(hv[0], hv[1], hv[2], hv[3]);
-#endif
-      }
-      jb += walk_dj; i += walk_di;
-      if (jb >= res) { jb -= res; ++i; }
+      if (g >= ngroups4) break;
+      // groups that touch the goal rectangle: their empty pixels still add the goal height to the union sum
+      const uint32_t inm = goal_mask4(w.i, w.jb, g0, g2, g1, g3);
+      if (inm) goalm |= 1u << k;
+      if ((L.rowmask[w.i >> 5] >> (w.i & 31)) & 1u) claim_group(L, g, k, cov);
+      else store_empty_group<DT>(C, g, (epair | zpair) ^ goal_pair(inm, gdiff), (epair | zpair) ^ goal_pair(inm >> 2, gdiff), inm);
+      w.step();
     }
   }
-  RSTAMP(5);
-  if (ext) return;
-  // ---- halving tree over the 512 partials: cross-wave stages through LDS, in-wave stages by shuffles
-#ifdef SRL_ABL_NOTAIL
-  if (P.px != 12345.0f) return;
-#endif
-  //      (p[t] += p[t + 256], t < 256; p[t] += p[t + 128], t < 128; p[t] += p[t + 64], t < 64; then shuffles): the three
-  //      cross-wave stages only ever combine lane t of the eight waves, so wave 0 reads the eight partials after ONE barrier
-  //      and adds them in the tree's order — the same sums, bit for bit, with two barriers fewer
+  return {cov, goalm};
+}
+
+// ---- ray cast of one item.  The S lanes of an item (adjacent, aligned) combine their partial minima with DPP moves folded
+//      into the min: within quads (lanes ^ 1, ^ 2), then across the two quads of a half row (mirror) — no LDS traffic
+template <int CTRL>
+__device__ __forceinline__ void combine_rows(f32x2 (&hh)[SRL_ITEM_ROWS], f32x2 (&ll)[SRL_ITEM_ROWS]) {
+#pragma unroll
+  for (int r = 0; r < SRL_ITEM_ROWS; ++r) {
+    hh[r].x = dpp_min<CTRL>(hh[r].x); hh[r].y = dpp_min<CTRL>(hh[r].y);
+    ll[r].x = dpp_min<CTRL>(ll[r].x); ll[r].y = dpp_min<CTRL>(ll[r].y);
+  }
+}
+__device__ __forceinline__ void lane_combine(int S, f32x2 (&hh)[SRL_ITEM_ROWS], f32x2 (&ll)[SRL_ITEM_ROWS]) {
+  if (S >= 2) combine_rows<0xB1>(hh, ll);
+  if (S >= 4) combine_rows<0x4E>(hh, ll);
+  if (S >= 8) combine_rows<0x141>(hh, ll);
+}
+
+// item p of rock b, shared by S lanes of which this is lane s: locate, sweep, lane combine, merge into the tile
+__device__ __forceinline__ void cast_item(const DevParams& P, const RenderCtx& C, const RenderLds& L, int b, int p, int s, int S) {
+  const int res = C.res;
+  const int4 pr = ((const int4*)L.prange)[b], rg = ((const int4*)L.reg)[b];
+  const int nir = pr.z, jj = pr.y, ii = pr.x;
+  const int j0 = jj & 0xffff, j1 = jj >> 16, i1 = ii >> 16;
+  int di, j;
+  if (nir > 0) {
+    // item row = the last one whose first item is <= p (rows the outline does not reach share their successor's first
+    // item, rows past the last start at the rock's item count); the row's first column is in the low byte
+    const int4* sp = (const int4*)(L.span + SRL_STAGE_SPANS * b);
+    const int4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
+    const int sv[SRL_STAGE_SPANS] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w, s3.x, s3.y, s3.z, s3.w};
+    const int key = (p << 8) | 0xff;
+    int w = sv[0];
+    di = 0;
+#pragma unroll
+    for (int r = 1; r < SRL_STAGE_SPANS; ++r) if (key >= sv[r]) { w = sv[r]; di = r; }
+    j = (w & 0xff) + 2 * (p - (w >> 8));
+  } else {
+    // items fill the bounding box.  p / w2 without the integer-division sequence: (p + 0.5) / w2 stays at least
+    // 0.5 / w2 >= 1 / 256 away from an integer, far more than the error of the reciprocal (p < 2^14, w2 <= 128)
+    const int w2 = (j1 - j0 + 2) >> 1;
+    di = (int)(((float)p + 0.5f) * __builtin_amdgcn_rcpf((float)w2));
+    j = j0 + 2 * (p - di * w2);
+  }
+  const int i = (ii & 0xffff) + SRL_ITEM_ROWS * di;
+  const bool col2 = j + 1 <= j1;
+  const f32x2 py = {((float)j + 0.5f) * P.px, ((float)(j + 1) + 0.5f) * P.px};
+  f32x2 vx[SRL_ITEM_ROWS], hh[SRL_ITEM_ROWS], ll[SRL_ITEM_ROWS];
+#pragma unroll
+  for (int r = 0; r < SRL_ITEM_ROWS; ++r) {
+    const float x = ((float)(i + r) + 0.5f) * P.px;
+    vx[r].x = x; vx[r].y = x; hh[r].x = 1e30f; hh[r].y = 1e30f; ll[r].x = 1e30f; ll[r].y = 1e30f;
+  }
+  // z_hi = min over the up-facing planes; inside the outline iff the smallest side function is >= 0
+  // the item row's ranges of the two lists (srl_k_stage): the faces / outline edges whose x extent reaches the row
+  const uint32_t rw = nir > 0 ? (uint32_t)L.range[SRL_STAGE_SPANS * b + di] : ((uint32_t)rg.y << 8) | ((uint32_t)rg.z << 24);
+  const int plo = rw & 0xff, pn = ((rw >> 8) & 0xff) - plo, slo = (rw >> 16) & 0xff, sn = (int)(rw >> 24) - slo;
+  plane_sweep<true>(L.planes + rg.x + plo, pn, s, S, py, vx, hh);
+  plane_sweep<true>(L.planes + rg.x + rg.y + slo, sn, s, S, py, vx, ll);
+  const bool lists = pn > 0 && sn > 0;           // (a row the lists do not reach holds no rock pixel)
+  lane_combine(S, hh, ll);
+  if (s == 0) {
+    // the tile holds codec-table rows, not heights: row(z) = codec_n - index of t = fl(FAR - z) is monotone in z,
+    // so the max over rocks commutes with the look-up and the epilogue needs no arithmetic per pixel (0 = no rock)
+    int* t0p = (int*)&L.tile[i * res + j];
+#pragma unroll
+    for (int r = 0; r < SRL_ITEM_ROWS; ++r) {
+      const bool rowok = i + r <= i1;
+      if (lists && rowok && ll[r].x >= 0.0f && hh[r].x > 0.0f) atomicMax(t0p + r * res, codec_row(hh[r].x, C.nearp, P.codec_n));
+      if (lists && rowok && col2 && ll[r].y >= 0.0f && hh[r].y > 0.0f) atomicMax(t0p + r * res + 1, codec_row(hh[r].y, C.nearp, P.codec_n));
+    }
+  }
+}
+
+// ---- ray cast of a rock group [bs, be): lanes over the flattened (rock, item of SRL_ITEM_ROWS x 2 pixels) list; when the list
+//      is short each item is shared by S adjacent lanes that split the planes and combine with shuffles
+__device__ __forceinline__ void cast_group(const DevParams& P, const RenderCtx& C, const RenderLds& L, int bs, int be) {
+  const int tid = C.tid;
+  // item counts of the group's rocks as running sums (registers, one LDS round trip); groups of more
+  // than 8 rocks fall back to walking the list
+  const bool few = be - bs <= 8;
+  int pre[8];
+  int total = 0;
+  if (few) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) pre[r] = bs + r < be ? L.prange[4 * (bs + r) + 3] : 0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) { total += pre[r]; pre[r] = total; }
+  } else {
+    for (int b = bs; b < be; ++b) total += L.prange[4 * b + 3];
+  }
+  int lg = 0;
+  while (lg < 3 && (total << (lg + 1)) <= SRL_RENDER_THREADS) ++lg;
+  const int S = 1 << lg, s = tid & (S - 1);
+  int wb = bs, wis = 0, wnib = few ? 0 : L.prange[4 * bs + 3];
+  for (int it = tid >> lg; it < total; it += SRL_RENDER_THREADS >> lg) {
+    int b, is;
+    if (few) {
+      b = bs; is = 0;
+#pragma unroll
+      for (int r = 0; r < 7; ++r) if (it >= pre[r]) { b = bs + r + 1; is = pre[r]; }
+    } else {
+      while (it >= wis + wnib) { wis += wnib; ++wb; wnib = L.prange[4 * wb + 3]; }
+      b = wb; is = wis;
+    }
+    cast_item(P, C, L, b, it - is, s, S);
+  }
+}
+
+// ---- next-group cursors: the extent [bs, be) of the group after the one that ended at bs, then its region cursors.
+//      Two block barriers: every thread has read the old cursors before they change, and sees the new ones after.
+__device__ __forceinline__ void next_group(const RenderCtx& C, const RenderLds& L, int bs, int& be) {
+  const int p0 = L.reg[4 * bs + 3];
+  while (be < C.nb && L.reg[4 * be + 3] + L.reg[4 * be + 1] + L.reg[4 * be + 2] - p0 <= SRL_PLANE_CAP) ++be;
+  __syncthreads();
+  if (C.tid >= bs && C.tid < be) L.reg[4 * C.tid + 0] = L.reg[4 * C.tid + 3] - p0;
+  __syncthreads();
+}
+
+// ---- epilogue: depth codec, H out, uint8 pack, IoU partial sums (4 pixels per thread per round, fixed order).
+//      The kernel is bound by VALU issue, so the pass is branch-free per pixel: the codec is one 8-byte look-up
+//      (DevParams::codec; a pixel without a rock reads the table's last entry, the empty-pixel constants), the goal
+//      terms are selected with bit masks.
+struct IouSums { float spi, spu; };
+// what the rounds of a thread share
+struct EpilogueConsts {
+  uint32_t todo;             // bit k: round k must be visited
+  uint32_t gp_lo, gp_hi;     // goal-channel bits of the thread's two observation words in a goal row (`aligned`)
+  float cu_in[4], ci_in[4];  // what the four pixels of a group no rock reaches add to the two sums in a goal row
+  float cu_out;              // ... and outside the goal rows (union sum only)
+};
+__device__ __forceinline__ EpilogueConsts epilogue_consts(const RenderCtx& C, uint32_t cov, uint32_t goalm) {
+  const float h_empty = C.h_empty, gz = C.gz;
+  EpilogueConsts K;
+  // An empty pixel outside the goal adds max(h_empty, 0) to the union sum and nothing else; when that is +0 (it is
+  // whenever FAR (FAR - max_z) is a float32, e.g. the default geometry) the addition is the identity, bit for bit
+  // (the partial sums never hold -0), so rounds whose group lies in a row no rock reaches and outside the goal
+  // rectangle are skipped altogether.
+  K.todo = fmaxf(h_empty, 0.0f) == 0.0f ? (cov | goalm) : 0xffffffffu;
+  K.gp_lo = goal_pair(C.colmask, C.gdiff); K.gp_hi = goal_pair(C.colmask >> 2, C.gdiff);
+  // (the columns are fixed per thread when `aligned`): the very terms the general path computes from the table's empty-pixel entry
+  K.cu_out = fmaxf(h_empty, 0.0f);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int m = __builtin_amdgcn_sbfe((int)C.colmask, t, 1);
+    K.cu_in[t] = fmaxf(h_empty, __int_as_float(__float_as_int(gz) & m));
+    K.ci_in[t] = __int_as_float(__float_as_int(fminf(h_empty, gz)) & m);
+  }
+  return K;
+}
+// round k of the pass: the thread's pixel group g = tid + 512 k at row i, columns jb .. jb + 3; returns the sums with its terms
+template <int DT>
+__device__ __forceinline__ IouSums epilogue_round(const DevParams& P, const RenderCtx& C, const RenderLds& L, const EpilogueConsts& K,
+                                                  uint32_t cov, int k, int i, int jb, IouSums U) {
+  const float gz = C.gz;
+  const uint32_t colmask = C.colmask, gdiff = C.gdiff, zpair = C.zpair;
+  const int g0 = C.g0, g2 = C.g2;
+  const bool aligned = C.aligned;
+  float spi = U.spi, spu = U.spu;
+  const uint2* __restrict__ ctab = P.codec;
+  const int g = C.tid + k * SRL_RENDER_THREADS;
+  if (!(((K.todo >> k) & 1u) && g < C.ngroups4)) return U;
+  const bool covg = (cov >> k) & 1u;
+  if (aligned && __builtin_amdgcn_ballot_w64(covg) == 0ull) {
+    // no group of the wave holds a rock pixel this round (their H / observation bytes left with the early stores):
+    // the sums take per-thread constants — no table look-ups, no stores
+    const bool rowin = (unsigned)(i - g0) < (unsigned)g2;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { spu += rowin ? K.cu_in[t] : K.cu_out; spi += rowin ? K.ci_in[t] : 0.0f; }
+    return {spi, spu};
+  }
+  uint4 r4 = make_uint4(0u, 0u, 0u, 0u);   // codec-table rows of the four pixels (0: no rock)
+  if (covg) r4 = ((const uint4*)L.tile)[g];
+  const uint32_t rw[4] = {r4.x, r4.y, r4.z, r4.w};
+  float hv[4]; uint32_t hb[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const uint2 en = *(const uint2*)((const char*)ctab + (rw[t] << 3));   // 32-bit offset from a uniform base
+    hv[t] = __uint_as_float(en.x); hb[t] = en.y;
+  }
+  // rewarder.py:297-307: goal pixels add min / max(h, goal) to the two sums, the others max(h, 0) to the union
+  // only (x + 0 = x bit for bit here: the partial sums never hold -0); m = all ones on a goal pixel
+  uint32_t glo = 0u, ghi = 0u;   // goal-channel bits of the two observation words
+  uint32_t gm = 0u;              // (other types: bit t = pixel t lies in the goal rectangle)
+  const bool rowin = (unsigned)(i - g0) < (unsigned)g2;
+  if (aligned && __builtin_amdgcn_ballot_w64(rowin && colmask != 0u) == 0ull) {
+    // none of the wave's groups of this round touches the goal (a wave covers whole rows): union sum only
+#pragma unroll
+    for (int t = 0; t < 4; ++t) spu += fmaxf(hv[t], 0.0f);
+  } else {
+    const uint32_t inm = aligned ? (rowin ? colmask : 0u) : goal_mask4(i, jb, g0, g2, C.g1, C.g3);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int m = __builtin_amdgcn_sbfe((int)inm, t, 1);
+      spu += fmaxf(hv[t], __int_as_float(__float_as_int(gz) & m));
+      spi += __int_as_float(__float_as_int(fminf(hv[t], gz)) & m);
+    }
+    if (aligned) { glo = rowin ? K.gp_lo : 0u; ghi = rowin ? K.gp_hi : 0u; }
+    else { glo = goal_pair(inm, gdiff); ghi = goal_pair(inm >> 2, gdiff); }
+    gm = inm;
+  }
+  if (covg) store_group<DT>(C, g, hv, (hb[0] | (hb[1] << 16) | zpair) ^ glo, (hb[2] | (hb[3] << 16) | zpair) ^ ghi, hb, gm);
+  return {spi, spu};
+}
+
+// ---- sum tree and reward (K5).  Halving tree over the 512 partials: cross-wave stages through LDS, in-wave stages by shuffles
+//      (p[t] += p[t + 256], t < 256; p[t] += p[t + 128], t < 128; p[t] += p[t + 64], t < 64; then shuffles): the three
+//      cross-wave stages only ever combine lane t of the eight waves, so wave 0 reads the eight partials after ONE barrier
+//      and adds them in the tree's order — the same sums, bit for bit, with two barriers fewer
+__device__ __forceinline__ void reward_tail(const DevParams& P, const RenderCtx& C, const RenderLds& L, const EpisodeWords& W,
+                                            float spi, float spu, float* __restrict__ reward, uint8_t* __restrict__ done) {
+  const int e = C.e, tid = C.tid, g2 = C.g2, g3 = C.g3;
+  const float gz = C.gz;
+  const float (&prev_m)[4] = W.prev_m;
+  EnvHdr* h = C.h;
+  const float* gb = P.blob + (size_t)e * P.BLOB;
   L.pi[tid] = spi; L.pu[tid] = spu;
   __syncthreads();
   float sum_i = 0.0f, sum_u = 0.0f;
@@ -863,7 +883,7 @@ __device__ __forceinline__ void render_body(DevParams P, const float4* __restric
   if (tid == 0) {
     const int K = P.c.metric == SRL_METRIC_ALL ? 4 : P.c.metric == SRL_METRIC_EVAL ? 2 : 1;
     float* rw = reward + (size_t)e * K;
-    if (mode == 0) {
+    if (W.mode == 0) {
       const float iou = sum_i / sum_u, orr = sum_i / ((float)(g2 * g3) * gz);
       if (P.c.metric == SRL_METRIC_ALL) {
         const float mv[4] = {iou, orr, discounted_metric(P, h, gb, SRL_METRIC_DIOU), discounted_metric(P, h, gb, SRL_METRIC_DOR)};
@@ -884,12 +904,65 @@ __device__ __forceinline__ void render_body(DevParams P, const float4* __restric
         rw[0] = (mv - pm) * P.scale;
         h->prev_metric[P.c.metric] = mv;
       }
-      done[e] = (uint8_t)hdone;
+      done[e] = (uint8_t)W.hdone;
     } else {   // reset step (env.py:235-236) or rejected action
       for (int m = 0; m < K; ++m) rw[m] = 0.0f;
       done[e] = 0;
     }
   }
+}
+
+// poses_ext != nullptr: test/profiling hook rendering explicit poses (srl_render_heightmap)
+// DT: the observation's element type (SRL_DTYPE_*); one kernel per type (srl_k_render = uint8, srl_k_render_u16 ...)
+template <int DT>
+__device__ __forceinline__ void render_body(DevParams P, const float4* __restrict__ stage, int slots, uint8_t* __restrict__ obs_map,
+                                            uint8_t* __restrict__ obs_obj, float* __restrict__ reward, uint8_t* __restrict__ done,
+                                            const int32_t* __restrict__ nb_ext, float* __restrict__ height_ext) {
+  extern __shared__ float4 lds_raw[];
+  const RenderLds L = render_lds(lds_raw, P.c.overhead_res * P.c.overhead_res);
+#ifdef SRL_STAMPS
+  const int e = blockIdx.x, tid = threadIdx.x;     // (RSTAMP names them)
+  long long _t0 = wall_clock64();
+#endif
+  RenderCtx C;
+  EpisodeWords W;
+  render_prologue<DT>(P, L, stage, slots, obs_map, nb_ext, height_ext, C, W);
+  if (!C.ext) object_observation<DT>(P, C, W, obs_obj);
+  __syncthreads();
+  RSTAMP(0);
+  // ---- groups of rocks whose planes fit the staging area
+  int bs = 0, be = L.misc[0];   // (be >= 1 when nb >= 1: a mesh has at most SRL_MAX_TRIS + 2 <= SRL_PLANE_CAP slots)
+  GroupBits G = {0u, 0u};
+  bool first = true;
+  do {
+    const StageFirst F = stage_first(C, L, bs, be);
+    RSTAMP(1);
+    if (first) {
+      G = early_stores<DT>(C, L);
+      RSTAMP(2);
+    }
+    stage_group(C, L, F, be);
+    __syncthreads();
+    if (be > bs) cast_group(P, C, L, bs, be);
+    __syncthreads();
+    RSTAMP(3);
+    first = false;
+    bs = be;
+    if (bs < C.nb) next_group(C, L, bs, be);
+  } while (bs < C.nb);
+  RSTAMP(4);
+  // ---- epilogue pass over the thread's pixel groups (the round loop stands here, not in a phase of its own: compiled apart
+  //      from this function it cost the uint8 kernel three spilled registers)
+  IouSums U = {0.0f, 0.0f};
+  const EpilogueConsts K = epilogue_consts(C, G.cov, G.goalm);
+  GroupWalk w(C);
+  for (int k = 0; k < C.nrounds; ++k) {
+    U = epilogue_round<DT>(P, C, L, K, G.cov, k, w.i, w.jb, U);
+    w.step();
+  }
+  RSTAMP(5);
+  if (C.ext) return;
+  reward_tail(P, C, L, W, U.spi, U.spu, reward, done);
   RSTAMP(6);
 }
 

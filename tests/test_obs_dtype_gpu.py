@@ -147,6 +147,49 @@ def test_wrap_quirk_at_the_top_of_the_window(ref_pool, oracle_mod, dtype):
   g.close()
 
 
+PLANE_CAP = 640                # SRL_PLANE_CAP (csrc/render.hip): plane / side slots of one rock group
+
+
+@pytest.mark.parametrize('dtype,kw,n,L', [
+  ('uint16', dict(resolution_factor=3), 6, 5),        # 32 x 32 map (1,024 pixels < 4 x 512 threads): the general walk with its
+  ('float64', dict(resolution_factor=3), 6, 5),       #   bound on the group index
+  ('uint16', dict(observable_size_ratio=3), 6, 5),    # 96 x 96 map: the general walk, whose groups change columns
+  ('float64', dict(observable_size_ratio=3), 6, 5),
+  ('float64', {}, 4, 14),                             # 14 rocks hold more slots than PLANE_CAP: a second rock group
+])
+def test_general_walk_and_later_groups_in_other_dtypes(ref_pool, oracle_mod, dtype, kw, n, L):
+  """The render kernel's stores of a type other than uint8 (element sizes 2 and 8) where the default 128 x 128 map with one
+  rock group does not take them: the early stores and the epilogue on the general pixel-group walk (maps whose width does not
+  divide 4 x 512, and maps smaller than one round of the workgroup), and the epilogue after a later rock group.  Every
+  observation through done and the auto-reset step is `_return` of the oracle's maps, bit for bit; rewards and done flags
+  are the oracle's."""
+  from stackrl_amd import env as envs
+  from stackrl_amd.config import StackConfig
+  seed = 31
+  g = envs.VecStackEnv(n_parallel=n, seed=seed, pool=ref_pool, block=True, episode_length=L, dtype=dtype, **kw)
+  cfg = StackConfig(n_envs=n, episode_length=L, dtype=dtype, **kw)
+  o = oracle_mod.OracleEnv(cfg, ref_pool, seed=seed)
+  res = 2 ** kw.get('resolution_factor', 5) * kw.get('observable_size_ratio', 4)
+  assert g.observation_spec[0].shape == (res, res, 2) and g.observation_spec[0].dtype == getattr(torch, dtype)
+  gout, oout = g.reset(), o.reset()
+  _check_obs(gout[0], o, oout[0], cfg, dtype, 'reset')
+  most_slots = 0
+  for k in range(L + 1):
+    a = g.sample()
+    assert np.array_equal(a.cpu().numpy(), o.sample())
+    gout = g.step(a)
+    oout = o.step(a.cpu().numpy())
+    tag = '{} {} step {}'.format(dtype, kw, k)
+    _check_obs(gout[0], o, oout[0], cfg, dtype, tag)
+    np.testing.assert_allclose(gout[1].cpu().numpy(), oout[1], rtol=0, atol=1e-7, err_msg=tag + ': reward')   # (test_parity_gpu's bound)
+    assert np.array_equal(gout[2].cpu().numpy(), oout[2]), tag + ': done'
+    hdr, nb = g.stage_records().view(np.int32)[:, :, 0], g.state()[1]    # per rock: ..., up-facing planes, outline sides
+    most_slots = max([most_slots] + [int(hdr[e, :int(nb[e]), 2:4].sum()) for e in range(n)])
+  if L == 14:
+    assert most_slots > PLANE_CAP, 'no env held more than one rock group ({} slots): the case is vacuous'.format(most_slots)
+  g.close()
+
+
 @pytest.mark.parametrize('dtype', ['float32', 'uint16'])
 @pytest.mark.parametrize('ordering', [False, True])
 def test_stack_v2_object_maps_in_other_dtypes(ref_pool, oracle_mod, dtype, ordering):

@@ -10,9 +10,8 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -- pyt
 python tools/pmc_summary.py $O/pmc_f $O/pmc_w srl_k_render 111656960 > $O/render_pmc.json || exit 1
 echo pmc done
 python tools/stamps_render.py > $O/stamps.txt 2>&1 || exit 1
-python tools/ab_render.py --libs ab_libs > $O/ablation.txt 2>&1 || exit 1
-echo ablation done
-bash tools/pmc_ablate.sh > $O/inst_counts.txt 2>&1 || exit 1
+# (the ablation timings and instruction counts of round 1 came from build switches that are retired:
+#  tools/experiments/render_ablation_switches.patch, profiles/README.md)
 echo all done
 # settle kernel counters (profiles/r01_settle_pmc.txt)
 cd /tmp && cd $GRAFT_REPO_ROOT
