@@ -1,5 +1,6 @@
 """The ctypes binding the native libraries share: one loader and one checked launch per library of `build.LIBRARIES`.
-lib.py, qops.py and compare.py keep their signature tables and get `load` and `call` from here."""
+Each wrapper module (lib.py, qops.py, compare.py, rocks.py, valueview.py, candidates.py) keeps its signature table and gets
+`load` and `call` from here."""
 import ctypes
 import os
 
@@ -13,14 +14,14 @@ def stream(t):
 
 
 def binding(library, sigs):
-  """(`load`, `call`) of `build.library(library)`.  `sigs`: export -> (restype, argtypes[, error accessor or None])."""
+  """(`load`, `call`) of `build.LIBRARIES[library]`. `sigs`: export -> (restype, argtypes[, error accessor or None])."""
   loaded = None
 
   def load():
     """Load (building first if the library is missing) and return the ctypes library; a symbol of `_SIGS` it lacks fails here."""
     nonlocal loaded
     if loaded is None:
-      path = _build.library(library).path     # read now, not at import: a diagnostic may have pointed it at another build
+      path = _build.LIBRARIES[library].path   # read now, not at import: a diagnostic may have pointed it at another build
       if not os.path.isfile(path):
         _build.build()
       lib = ctypes.CDLL(path)

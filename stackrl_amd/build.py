@@ -147,23 +147,14 @@ LIBRARIES = {
                           'conv_gemm.hip', 'learner.hip', 'train_conv.hip'], QFLAGS, ('no-slp',)),
   # the policy-comparison statistics (include/stackrl_compare.h): a library of its own, so that libstackrl_qnet.so keeps its exports
   'compare': _library(CLIB, ['compare.hip'], QFLAGS, ('no-slp',)),
-}
-# The asset side, off the training path: the procedural rock generator (include/stackrl_rocks.h), a library of its own like
-# `compare`.  It has a table of its own because tests/test_isa_guard.py holds `LIBRARIES` to a per-library census it lists by
-# name; tests/test_rocks_abi.py applies the same guard to this one.  `library(name)` looks through both, and `deps`,
-# `source_hash`, `stale`, `build_library`, `build` and `_bind.binding` go through it.
-ASSET_LIBRARIES = {
+  # off the training path, each a library of its own like `compare`: the procedural rock generator (include/stackrl_rocks.h),
   'rocks': _library(RLIB, ['rocks.hip'], QFLAGS, ('no-slp',)),
-  # the frames of a visualised comparison run (include/stackrl_valueview.h); tests/test_valueview_abi.py holds its guard
+  # the frames of a visualised comparison run (include/stackrl_valueview.h),
   'valueview': _library(VLIB, ['valueview.hip'], QFLAGS, ('no-slp',)),
-  # the spread candidates of a lookahead (include/stackrl_candidates.h); tests/test_candidates_abi.py holds its guard
+  # and the spread candidates of a lookahead (include/stackrl_candidates.h)
   'candidates': _library(KLIB, ['candidates.hip'], QFLAGS, ('no-slp',)),
 }
 QSRC = LIBRARIES['qnet'].sources
-
-
-def library(name):
-  return LIBRARIES[name] if name in LIBRARIES else ASSET_LIBRARIES[name]
 
 
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
@@ -172,7 +163,7 @@ _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
 def deps(name, root=ROOT):
   """The files library `name` is built from, relative to `root` (the repository, or a copy of it) and sorted: its sources,
   whatever they reach through `#include "..."` lines (each resolved against the including file), and its recipe files."""
-  lib = library(name)
+  lib = LIBRARIES[name]
   seen, todo = set(lib.recipe), [os.path.join('stackrl_amd', 'csrc', s) for s in lib.sources]
   while todo:
     d = todo.pop()
@@ -190,25 +181,25 @@ def source_hash(name, root=ROOT):
   for d in deps(name, root):
     with open(os.path.join(root, d), 'rb') as f:
       h.update(d.encode() + b'\0' + f.read() + b'\0')
-  h.update(' '.join(library(name).flags).encode())
+  h.update(' '.join(LIBRARIES[name].flags).encode())
   return h.hexdigest()[:16]
 
 
 def stale(name):
   """The library is missing, or was not built from these sources with these flags (the hash it carries, not file times)."""
-  i = info(library(name).path)
+  i = info(LIBRARIES[name].path)
   return i is None or i['hash'] != source_hash(name)
 
 
 def build_library(name, out=None, verbose=False):
   """Build library `name` to `out` (default: its place in the tree)."""
-  lib = library(name)
+  lib = LIBRARIES[name]
   lib.compile(lib, os.environ.get('HIPCC', '/opt/rocm/bin/hipcc'), source_hash(name), out or lib.path, verbose)
 
 
 def build(force=False, verbose=False):
   """Build every library that is missing or stale (all of them with `force`); returns the env library's path."""
-  for name in list(LIBRARIES) + list(ASSET_LIBRARIES):
+  for name in LIBRARIES:
     if force or stale(name):
       build_library(name, verbose=verbose)
   return LIBRARIES['env'].path

@@ -15,7 +15,7 @@ MAX_K = 32
 
 _VP, _I32, _INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int
 # export -> (restype, argtypes, error accessor or None): every declaration of include/stackrl_candidates.h (pointers as void*);
-# tests/test_candidates_abi.py holds the table to the header and the library.
+# tests/test_abi.py holds the table to the header and the library.
 _SIGS = {
   'srl_candidates_select': (_INT, [_VP, _I32, _VP] + [_I32] * 6 + [_VP] * 3, 'srl_candidates_last_error'),
   'srl_candidates_last_error': (ctypes.c_char_p, [], None),

@@ -24,7 +24,7 @@ HOLD = -2          # SRL_ACTION_HOLD (include/srl_types.h): the env sits a call 
 
 _VP, _I32, _INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int
 # export -> (restype, argtypes, error accessor or None): every declaration of include/stackrl_compare.h (pointers as void*);
-# tests/test_compare_abi.py holds the table to the header and the library.  The launching export returns int and takes the
+# tests/test_abi.py holds the table to the header and the library.  The launching export returns int and takes the
 # stream last.
 _SIGS = {
   'srl_compare_record_doubles': (_I32, [_I32], None),

@@ -30,7 +30,7 @@ class Params(ctypes.Structure):
 
 _VP, _I32, _I64, _INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
 # export -> (restype, argtypes, error accessor or None): every declaration of include/stackrl_rocks.h (pointers as void*);
-# tests/test_rocks_abi.py holds the table to the header and the library.
+# tests/test_abi.py holds the table to the header and the library.
 _SIGS = {
   'srl_rocks_points': (_INT, [_I32, _VP], None),
   'srl_rocks_generate': (_INT, [_VP, _I64, _I32, _VP, _I32] + [_VP] * 11, 'srl_rocks_last_error'),

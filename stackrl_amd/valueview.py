@@ -19,7 +19,7 @@ MAX_SCALE = 8
 
 _VP, _I32, _INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int
 # export -> (restype, argtypes, error accessor or None): every declaration of include/stackrl_valueview.h (pointers as void*);
-# tests/test_valueview_abi.py holds the table to the header and the library.
+# tests/test_abi.py holds the table to the header and the library.
 _SIGS = {
   'srl_valueview_layout': (_INT, [_I32] * 4 + [_VP], 'srl_valueview_last_error'),
   'srl_valueview_window': (_INT, [_I32, _I32, _VP], 'srl_valueview_last_error'),

@@ -1,26 +1,69 @@
-"""CPU tests of the boundary: the C-ABI library builds for gfx950, loads, and exports every symbol that
-include/stackrl_hip.h declares (no compute calls: there is no GPU here)."""
+"""CPU tests of the boundary every native library keeps (no compute calls: there is no GPU here): the header(s), the ctypes
+table and the exported symbols agree, and the library carries the hash of its sources, stated once over
+`build.LIBRARIES` with what differs between the libraries in tests/library_boundary.py; then what only the env and the Q-net
+library have.  The dependency sets are held in tests/test_build_deps.py and the packed-fp32 guard in tests/test_isa_guard.py."""
 import ctypes
 import os
 import re
 
 import pytest
 
+import library_boundary as boundary
+from stackrl_amd import build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = sorted(build.LIBRARIES)
 
 
-def _declared():
-  with open(os.path.join(ROOT, 'include', 'stackrl_hip.h')) as f:
-    txt = f.read()
-  return sorted(set(re.findall(r'\b(srl_[a-z0-9_]+)\s*\(', txt)))
+@pytest.mark.parametrize('name', NAMES)
+def test_header_table_and_exports_agree(name):
+  """`_SIGS` names exactly the exports the headers declare, each with the declaration's return and argument types and the
+  accessor of the row's rule; the library exports them, and its sources define each once."""
+  row, sigs = boundary.ROWS[name], boundary.module(name)._SIGS
+  build.build()                                   # a no-op unless a library is missing or stale
+  decl = boundary.declarations(row.headers)
+  assert sorted(sigs) == sorted(decl), 'ctypes signature table out of sync with the header'
+  assert row.names is None or sorted(decl) == row.names
+  assert row.build_info in decl and set(row.host_only) <= set(decl)
+  for export, (ret, params) in decl.items():
+    if row.untyped:
+      continue
+    assert sigs[export][0] is boundary.ctype(ret, ret=True), export
+    assert list(sigs[export][1]) == [boundary.ctype(p) for p in params], export
+    # the launching exports: the stream goes last (what `_bind.binding`'s `call` appends)
+    assert (ret == 'int' and export not in row.host_only) == (''.join(params[-1:]).replace(' ', '') == 'void*stream'), export
+    if row.accessor:
+      assert sigs[export][2] == row.accessor(export, ret), export
+  # the library exports these (and, without a reason for more, nothing else of the project's), each defined once in its sources
+  exported, defined = boundary.exports(name), boundary.defined(name)
+  assert set(decl) <= set(exported) and set(decl) <= set(defined)
+  if not row.extra:
+    assert exported == sorted(decl) == sorted(defined)
+  assert all(ret == decl[export][0] for export, (_, ret) in defined.items() if export in decl)
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_library_carries_the_hash_of_its_sources(name):
+  row, lib = boundary.ROWS[name], build.LIBRARIES[name]
+  build.build()                                   # a no-op unless a library is missing or stale
+  i = build.info(lib.path)
+  assert i is not None and i['variant'] in lib.variants and i['hash'] == build.source_hash(name)
+  assert not build.stale(name)
+  said = getattr(boundary.module(name).load(), row.build_info)().decode()
+  assert said == 'SRL_BUILD_INFO<{}|{}>'.format(i['variant'], i['hash'])
+  # only the env library is compiled with the SLP vectoriser (and rewritten, or built the safe way)
+  assert lib.flags is (build.FLAGS if name == 'env' else build.QFLAGS) and '-fno-slp-vectorize' in build.QFLAGS
+  assert lib.variants == ((build.VARIANT_FIXED, build.VARIANT_SAFE) if name == 'env' else ('no-slp',))
+  if row.deps is not None:                        # the hash follows the header(s) and the one source, named here
+    assert build.deps(name) == row.deps and lib.sources == [os.path.basename(row.deps[-1])]
 
 
 def test_library_builds_and_exports_every_declared_symbol():
-  from stackrl_amd import build, lib
+  from stackrl_amd import lib
   path = build.build()
   assert os.path.isfile(path)
   L = ctypes.CDLL(path)
-  names = _declared()
+  names = sorted(boundary.declarations(boundary.ROWS['env'].headers))
   assert len(names) >= 18
   for n in names:
     assert hasattr(L, n), 'missing export ' + n
@@ -28,10 +71,8 @@ def test_library_builds_and_exports_every_declared_symbol():
 
 
 def test_qnet_library_exports_every_declared_symbol():
-  from stackrl_amd import build
   build.build()
-  with open(os.path.join(ROOT, 'include', 'stackrl_qnet.h')) as f:
-    names = sorted(set(re.findall(r'\b(srl_[a-z0-9_]+)\s*\(', f.read())))
+  names = sorted(boundary.declarations(('stackrl_qnet.h',)))
   assert names == ['srl_adam_step', 'srl_baseline_select', 'srl_bias_act', 'srl_bias_act_bwd_f32', 'srl_bias_act_bwd_scratch_floats', 'srl_bias_act_f32', 'srl_bias_act_pool', 'srl_bias_act_pool_f32', 'srl_conv3x3_bias_relu', 'srl_conv3x3_bias_relu_f32', 'srl_conv3x3_gemm_batch_multiple', 'srl_conv3x3_gemm_bias_relu', 'srl_conv3x3_gemm_supported', 'srl_conv3x3_gemm_wfrag_elems', 'srl_conv3x3_relu_project', 'srl_conv3x3_relu_project_f32', 'srl_conv3x3_thin', 'srl_conv3x3_thin_f32', 'srl_conv3x3_wfrag_elems', 'srl_conv_gemm_last_error',
                    'srl_conv_last_error', 'srl_convt2x2_bias_relu', 'srl_convt2x2_bias_relu_f32', 'srl_convt2x2_gemm_bias_relu', 'srl_convt2x2_gemm_supported', 'srl_convt2x2_wfrag_elems', 'srl_epilogue_last_error', 'srl_gumbel_topk',
                    'srl_gumbel_topk_scratch_bytes', 'srl_heuristic', 'srl_learner_last_error', 'srl_logit_extrema', 'srl_logit_extrema_scratch_bytes',
@@ -43,59 +84,20 @@ def test_qnet_library_exports_every_declared_symbol():
     assert hasattr(L, n), 'missing export ' + n
 
 
-QNET_HEADERS = ('stackrl_qnet.h', 'stackrl_explore.h', 'stackrl_greedy.h', 'stackrl_baseline_rows.h')
-
-
-def _qnet_declarations():
-  """name -> (return type, [parameter declarations]) of every `ret name(params);` of the four Q-net headers, comments and
-  preprocessor lines stripped."""
-  out = {}
-  for h in QNET_HEADERS:
-    with open(os.path.join(ROOT, 'include', h)) as f:
-      txt = f.read()
-    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    txt = re.sub(r'//[^\n]*', '', txt)
-    txt = re.sub(r'^\s*#[^\n]*', '', txt, flags=re.M).replace('extern "C" {', '')
-    for ret, name, params in re.findall(r'([A-Za-z_][\w\s\*]*?)\b(srl_\w+)\s*\(([^)]*)\)\s*;', txt):
-      assert name not in out, name + ' is declared twice'
-      params = [' '.join(p.split()) for p in params.split(',')]
-      out[name] = (' '.join(ret.split()), [] if params == ['void'] else params)
-  return out
-
-
-def _ctype(decl, ret=False):
-  """The ctypes type of a return type or a parameter declaration: any pointer is void*, but a returned const char* a string."""
-  if '*' in decl:
-    return ctypes.c_char_p if ret and decl.replace(' ', '') == 'constchar*' else ctypes.c_void_p
-  base = [t for t in decl.split() if t != 'const'][0]
-  return {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'double': ctypes.c_double, 'int': ctypes.c_int}[base]
-
-
 def test_qnet_signature_table_matches_the_headers():
-  """`qops._SIGS` names exactly the exports the four headers declare, each with the declaration's return and argument types."""
+  """`qops._SIGS` names the 67 exports the four headers declare (their types: test_header_table_and_exports_agree[qnet])."""
   from stackrl_amd import qops
-  decl = _qnet_declarations()
-  assert len(decl) == 67
-  assert sorted(qops._SIGS) == sorted(decl)
-  for name, (ret, params) in decl.items():
-    res, args, _ = qops._SIGS[name]
-    assert res is _ctype(ret, ret=True), name
-    assert list(args) == [_ctype(p) for p in params], name
-    if ret == 'int':               # the launching exports: the stream goes last (what `qops.call` appends)
-      assert params[-1].replace(' ', '') == 'void*stream', name
+  decl = boundary.declarations(boundary.ROWS['qnet'].headers)
+  assert len(boundary.ROWS['qnet'].headers) == 4 and len(decl) == 67 and sorted(qops._SIGS) == sorted(decl)
 
 
 def test_qnet_error_accessors_match_the_sources():
   """Every .hip file keeps its own error text: the accessor the table names for an export is the one of the file that defines
   the export (qnet.hip, greedy.hip and heuristics.hip share `srl_qnet_last_error` through `srl_qnet_set_error`)."""
-  from stackrl_amd import build, qops
-  where, launches = {}, {}
-  for f in build.QSRC:
-    with open(os.path.join(build.CSRC, f)) as fh:
-      for ret, name in re.findall(r'^(const char\*|int|int32_t|int64_t)\s+(srl_\w+)\s*\(', fh.read(), re.M):
-        assert name not in where, name + ' is defined twice'
-        where[name] = f
-        launches[name] = ret == 'int'    # status returns; the size and support queries return int32_t / int64_t
+  from stackrl_amd import qops
+  defined = boundary.defined('qnet')
+  where = {n: f for n, (f, _) in defined.items()}
+  launches = {n: ret == 'int' for n, (_, ret) in defined.items()}    # status returns; the size and support queries return int32_t / int64_t
   assert len(where) == 67 and len(set(where.values())) == 9
   assert sorted(where) == sorted(qops._SIGS)
   own = {f: [n for n, g in where.items() if g == f and n.endswith('_last_error')] for f in build.QSRC}

@@ -1,40 +1,30 @@
 """What a library is built from is derived (stackrl_amd/build.py `deps`: the sources, the closure of their quoted includes,
 the recipe files), and its hash and `stale` follow that set.  The compiler is the reference for the set: `hipcc -MM` names the
-files it reads for a source.  No GPU needed."""
+files it reads for a source (tests/library_boundary.py `compiler_deps`).  No GPU needed."""
+import itertools
 import os
-import re
 import shutil
-import subprocess
 
 import pytest
 
+import library_boundary as boundary
 from stackrl_amd import build
 
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 NAMES = sorted(build.LIBRARIES)
-
-
-def _compiler_deps(name):
-  """The project's files that the compiler reads for the library's sources with the library's flags, relative to the
-  repository, plus the recipe files."""
-  lib = build.LIBRARIES[name]
-  keep = [f for f in lib.flags if f not in ('-shared', '-fPIC')]
-  out = set(lib.recipe)
-  for s in lib.sources:
-    mm = subprocess.run([HIPCC] + keep + ['--cuda-host-only', '-MM', '-w', os.path.join(build.CSRC, s)], check=True,
-                        stdout=subprocess.PIPE, universal_newlines=True).stdout
-    files = re.sub(r'\\\n', ' ', mm).split(':', 1)[1].split()
-    out.update(os.path.relpath(os.path.realpath(f), os.path.realpath(build.ROOT)) for f in files)
-  assert not any(d.startswith('..') for d in out), out         # -MM leaves system headers out
-  return sorted(out)
 
 
 @pytest.mark.parametrize('name', NAMES)
 def test_the_derived_set_is_the_compilers(name):
-  assert build.deps(name) == _compiler_deps(name)
+  assert build.deps(name) == boundary.compiler_deps(name)
   if name == 'env':
     assert os.path.join('stackrl_amd', 'csrc', 'stage.h') in build.deps('env')
     assert os.path.join('stackrl_amd', 'csrc', 'solver.h') in build.deps('env')
+
+
+def test_no_two_libraries_share_a_file_but_the_types():
+  """A library's sources, headers and recipe are its own: a change to one library's files rebuilds no other."""
+  for a, b in itertools.combinations(NAMES, 2):
+    assert set(build.deps(a)) & set(build.deps(b)) <= {boundary.TYPES}, (a, b)
 
 
 def _copy(tmp_path):
@@ -56,12 +46,12 @@ def test_the_hash_follows_every_file_of_the_set_and_no_other(tmp_path):
       with open(os.path.join(root, d), 'ab') as f:
         f.write(b'\n')
       assert build.source_hash(name, root) != before, (name, d)
-  # a file outside the set
+  # a file outside the set of every library but one
   before = {name: build.source_hash(name, root) for name in NAMES}
   with open(os.path.join(root, 'stackrl_amd', 'csrc', 'compare.hip'), 'ab') as f:
     f.write(b'\n')
-  after = {name: build.source_hash(name, root) for name in NAMES}
-  assert after['env'] == before['env'] and after['qnet'] == before['qnet'] and after['compare'] != before['compare']
+  for name in NAMES:
+    assert (build.source_hash(name, root) != before[name]) == (name == 'compare'), name
 
 
 def test_after_a_build_no_library_is_stale():

@@ -1,108 +1,19 @@
-"""CPU tests of the boundary of libstackrl_candidates.so: header <-> `candidates._SIGS` <-> the library's exports, the hash the
-library carries, its refusals (each with a text of its own, none of which launches anything), and the packed-fp32 guard of
-DESIGN.md section 6a on csrc/candidates.hip and on the shipped library (tests/test_isa_guard.py walks `build.LIBRARIES`; this
-library stands in `build.ASSET_LIBRARIES`)."""
-import ctypes
+"""CPU tests of what only libstackrl_candidates.so has at its boundary: the limits of its header, and its refusals (each with
+a text of its own, none of which launches anything).  The boundary it shares with the other libraries is held in
+tests/test_abi.py, tests/test_build_deps.py and tests/test_isa_guard.py."""
 import os
 import re
-import subprocess
 
 import candidates_cases as cases
-from stackrl_amd import build, isa_fix
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-EXPORTS = ['srl_candidates_build_info', 'srl_candidates_last_error', 'srl_candidates_select']
-SOURCE = os.path.join(build.CSRC, 'candidates.hip')
-HEADER = os.path.join(ROOT, 'include', 'stackrl_candidates.h')
+from stackrl_amd import build
 
 
-def _declarations():
-  """name -> (return type, [parameter declarations]) of every `ret name(params);` of include/stackrl_candidates.h."""
-  with open(HEADER) as f:
-    txt = f.read()
-  txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-  txt = re.sub(r'^\s*#[^\n]*', '', txt, flags=re.M).replace('extern "C" {', '')
-  out = {}
-  for ret, name, params in re.findall(r'([A-Za-z_][\w\s\*]*?)\b(srl_\w+)\s*\(([^)]*)\)\s*;', txt):
-    assert name not in out
-    params = [' '.join(p.split()) for p in params.split(',')]
-    out[name] = (' '.join(ret.split()), [] if params == ['void'] else params)
-  return out
-
-
-def _ctype(decl, ret=False):
-  if '*' in decl:
-    return ctypes.c_char_p if ret and decl.replace(' ', '') == 'constchar*' else ctypes.c_void_p
-  base = [t for t in decl.split() if t != 'const'][0]
-  return {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'int': ctypes.c_int}[base]
-
-
-def test_header_table_and_exports_agree():
+def test_the_limits_of_the_header_are_the_bindings_and_the_restatements():
   from stackrl_amd import candidates
-  build.build()
-  decl = _declarations()
-  assert sorted(decl) == EXPORTS and sorted(candidates._SIGS) == EXPORTS
-  for name, (ret, params) in decl.items():
-    res, args, err = candidates._SIGS[name]
-    assert res is _ctype(ret, ret=True), name
-    assert list(args) == [_ctype(p) for p in params], name
-    assert err == (None if res is ctypes.c_char_p else 'srl_candidates_last_error'), name
-  assert decl['srl_candidates_select'][1][-1].replace(' ', '') == 'void*stream'
-  # the library exports these and nothing else of the project's; each is defined once, in its one source file
-  nm = subprocess.run(['nm', '-D', '--defined-only', build.KLIB], check=True, stdout=subprocess.PIPE, universal_newlines=True).stdout
-  assert sorted(set(re.findall(r'\b(srl_\w+)', nm))) == EXPORTS
-  with open(SOURCE) as f:
-    defined = re.findall(r'^(?:const char\*|int|int32_t)\s+(srl_\w+)\s*\(', f.read(), re.M)
-  assert sorted(defined) == EXPORTS and build.library('candidates').sources == ['candidates.hip']
-  # the limits of the header are the binding's and the restatement's
-  with open(HEADER) as f:
+  with open(os.path.join(build.ROOT, 'include', 'stackrl_candidates.h')) as f:
     limits = dict(re.findall(r'^#define (SRL_CANDIDATES_\w+) (\d+)', f.read(), re.M))
   assert int(limits['SRL_CANDIDATES_MAX_K']) == candidates.MAX_K == cases.MAX_K == 32
   assert int(limits['SRL_CANDIDATES_THREADS']) == cases.THREADS
-  # an asset library, and the other libraries are what they were
-  assert 'candidates' in build.ASSET_LIBRARIES and 'candidates' not in build.LIBRARIES
-  assert build.library('candidates') is build.ASSET_LIBRARIES['candidates']
-  assert not any('candidates' in d for name in build.LIBRARIES for d in build.deps(name))
-  assert not any('candidates' in d for name in ('rocks', 'valueview') for d in build.deps(name))
-
-
-def test_library_carries_the_hash_of_its_sources():
-  from stackrl_amd import candidates
-  build.build()                                   # a no-op unless a library is missing or stale
-  i = build.info(build.KLIB)
-  assert i is not None and i['variant'] == 'no-slp' and i['hash'] == build.source_hash('candidates')
-  assert not build.stale('candidates')
-  assert candidates.load().srl_candidates_build_info().decode() == 'SRL_BUILD_INFO<no-slp|{}>'.format(i['hash'])
-  assert build.library('candidates').flags is build.QFLAGS
-  assert build.deps('candidates') == [os.path.join('include', 'srl_types.h'), os.path.join('include', 'stackrl_candidates.h'),
-                                      os.path.join('stackrl_amd', 'csrc', 'candidates.hip')]
-
-
-def test_the_derived_set_is_the_compilers_and_the_hash_follows_it(tmp_path):
-  """What tests/test_build_deps.py holds for the libraries of `build.LIBRARIES`, for this one: `deps` names the project's files
-  `hipcc -MM` reads, and the hash moves with each of them and with no file of another library."""
-  import shutil
-  lib = build.library('candidates')
-  keep = [f for f in lib.flags if f not in ('-shared', '-fPIC')]
-  mm = subprocess.run([HIPCC] + keep + ['--cuda-host-only', '-MM', '-w', SOURCE], check=True, stdout=subprocess.PIPE,
-                      universal_newlines=True).stdout
-  files = re.sub(r'\\\n', ' ', mm).split(':', 1)[1].split()
-  assert build.deps('candidates') == sorted(os.path.relpath(os.path.realpath(f), os.path.realpath(build.ROOT)) for f in files)
-  for d in build.deps('candidates') + build.deps('compare'):
-    os.makedirs(os.path.dirname(str(tmp_path / d)), exist_ok=True)
-    shutil.copy(os.path.join(build.ROOT, d), str(tmp_path / d))
-  root = str(tmp_path)
-  assert build.source_hash('candidates', root) == build.source_hash('candidates')
-  for d in build.deps('candidates'):
-    before = build.source_hash('candidates', root)
-    with open(os.path.join(root, d), 'ab') as f:
-      f.write(b'\n')
-    assert build.source_hash('candidates', root) != before, d
-  before = build.source_hash('candidates', root)
-  with open(os.path.join(root, 'stackrl_amd', 'csrc', 'compare.hip'), 'ab') as f:
-    f.write(b'\n')
-  assert build.source_hash('candidates', root) == before
 
 
 def test_each_refusal_has_its_own_text_and_launches_nothing():
@@ -140,13 +51,3 @@ def test_each_refusal_has_its_own_text_and_launches_nothing():
   assert 'cand 0' in refused(G=3, OH=2, n_valid=1, k=5, cand=None)
   # the largest k, radius and map the checks admit are not refused for their size: the null output is
   assert 'cand 0' in refused(G=1, OH=46340, n_valid=1, k=32, radius=2 ** 31 - 1, cand=None)
-
-
-def test_no_kernel_of_the_library_contains_the_flagged_packed_form():
-  text = build.device_asm(HIPCC, build.QFLAGS, SOURCE)
-  assert not isa_fix.flagged(text)
-  assert text.count('k_candidates') >= 2 and text.count('s_barrier') >= 4          # the scan saw both kernels
-  build.build()
-  texts = isa_fix.shipped_asm(build.KLIB)
-  assert len(texts) == 1 and not isa_fix.flagged(texts[0])
-  assert texts[0].count('k_candidates') >= 2 and texts[0].count('s_barrier') >= 4

@@ -1,107 +1,18 @@
-"""CPU tests of the boundary of libstackrl_valueview.so: header <-> `valueview._SIGS` <-> the library's exports, the hash the
-library carries, its host-only exports (the layout, the window and the colour table, held to tests/value_view_cases.py and the
-matplotlib fixture), its refusals (each with a text of its own, none of which launches anything), and the packed-fp32 guard of
-DESIGN.md section 6a on csrc/valueview.hip and on the shipped library (tests/test_isa_guard.py walks `build.LIBRARIES`; this
-library stands in `build.ASSET_LIBRARIES`)."""
+"""CPU tests of what only libstackrl_valueview.so has at its boundary: its host-only exports (the layout, the window and the
+colour table, held to tests/value_view_cases.py and the matplotlib fixture), its limit, and its refusals (each with a text of
+its own, none of which launches anything).  The boundary it shares with the other libraries is held in tests/test_abi.py,
+tests/test_build_deps.py and tests/test_isa_guard.py."""
 import ctypes
 import itertools
-import os
-import re
-import subprocess
 
 import numpy as np
 
 import value_view_cases as cases
-from stackrl_amd import build, isa_fix
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-EXPORTS = ['srl_valueview_build_info', 'srl_valueview_frames', 'srl_valueview_last_error', 'srl_valueview_layout',
-           'srl_valueview_lut', 'srl_valueview_window']
-SOURCE = os.path.join(build.CSRC, 'valueview.hip')
 
 
-def _declarations():
-  """name -> (return type, [parameter declarations]) of every `ret name(params);` of include/stackrl_valueview.h."""
-  with open(os.path.join(ROOT, 'include', 'stackrl_valueview.h')) as f:
-    txt = f.read()
-  txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-  txt = re.sub(r'^\s*#[^\n]*', '', txt, flags=re.M).replace('extern "C" {', '')
-  out = {}
-  for ret, name, params in re.findall(r'([A-Za-z_][\w\s\*]*?)\b(srl_\w+)\s*\(([^)]*)\)\s*;', txt):
-    assert name not in out
-    params = [' '.join(p.split()) for p in params.split(',')]
-    out[name] = (' '.join(ret.split()), [] if params == ['void'] else params)
-  return out
-
-
-def _ctype(decl, ret=False):
-  if '*' in decl:
-    return ctypes.c_char_p if ret and decl.replace(' ', '') == 'constchar*' else ctypes.c_void_p
-  base = [t for t in decl.split() if t != 'const'][0]
-  return {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'int': ctypes.c_int}[base]
-
-
-def test_header_table_and_exports_agree():
-  from stackrl_amd import valueview
-  build.build()
-  decl = _declarations()
-  assert sorted(decl) == EXPORTS and sorted(valueview._SIGS) == EXPORTS
-  for name, (ret, params) in decl.items():
-    res, args, err = valueview._SIGS[name]
-    assert res is _ctype(ret, ret=True), name
-    assert list(args) == [_ctype(p) for p in params], name
-    assert err == (None if res is ctypes.c_char_p else 'srl_valueview_last_error'), name
-  assert decl['srl_valueview_frames'][1][-1].replace(' ', '') == 'void*stream'
-  # the library exports these and nothing else of the project's; each is defined once, in its one source file
-  nm = subprocess.run(['nm', '-D', '--defined-only', build.VLIB], check=True, stdout=subprocess.PIPE, universal_newlines=True).stdout
-  assert sorted(set(re.findall(r'\b(srl_\w+)', nm))) == EXPORTS
-  with open(SOURCE) as f:
-    defined = re.findall(r'^(?:const char\*|int|int32_t)\s+(srl_\w+)\s*\(', f.read(), re.M)
-  assert sorted(defined) == EXPORTS and build.library('valueview').sources == ['valueview.hip']
-  # the limits are the comparison's, the library is an asset library, and the other libraries are what they were
-  from stackrl_amd import compare
+def test_the_limit_is_the_comparisons():
+  from stackrl_amd import compare, valueview
   assert valueview.MAX_POLICIES == compare.MAX_POLICIES == 8
-  assert 'valueview' in build.ASSET_LIBRARIES and 'valueview' not in build.LIBRARIES
-  assert build.library('valueview') is build.ASSET_LIBRARIES['valueview']
-  assert not any('valueview' in d for name in build.LIBRARIES for d in build.deps(name))
-  assert not any('valueview' in d for d in build.deps('rocks'))
-
-
-def test_library_carries_the_hash_of_its_sources():
-  from stackrl_amd import valueview
-  build.build()                                   # a no-op unless a library is missing or stale
-  i = build.info(build.VLIB)
-  assert i is not None and i['variant'] == 'no-slp' and i['hash'] == build.source_hash('valueview')
-  assert not build.stale('valueview')
-  assert valueview.load().srl_valueview_build_info().decode() == 'SRL_BUILD_INFO<no-slp|{}>'.format(i['hash'])
-  assert build.library('valueview').flags is build.QFLAGS
-  assert build.deps('valueview') == [os.path.join('include', 'srl_types.h'), os.path.join('include', 'stackrl_valueview.h'),
-                                     os.path.join('stackrl_amd', 'csrc', 'valueview.hip')]
-
-
-def test_the_derived_set_is_the_compilers_and_the_hash_follows_it(tmp_path):
-  import shutil
-  lib = build.library('valueview')
-  keep = [f for f in lib.flags if f not in ('-shared', '-fPIC')]
-  mm = subprocess.run([HIPCC] + keep + ['--cuda-host-only', '-MM', '-w', SOURCE], check=True, stdout=subprocess.PIPE,
-                      universal_newlines=True).stdout
-  files = re.sub(r'\\\n', ' ', mm).split(':', 1)[1].split()
-  assert build.deps('valueview') == sorted(os.path.relpath(os.path.realpath(f), os.path.realpath(build.ROOT)) for f in files)
-  for d in build.deps('valueview') + build.deps('compare'):
-    os.makedirs(os.path.dirname(str(tmp_path / d)), exist_ok=True)
-    shutil.copy(os.path.join(build.ROOT, d), str(tmp_path / d))
-  root = str(tmp_path)
-  assert build.source_hash('valueview', root) == build.source_hash('valueview')
-  for d in build.deps('valueview'):
-    before = build.source_hash('valueview', root)
-    with open(os.path.join(root, d), 'ab') as f:
-      f.write(b'\n')
-    assert build.source_hash('valueview', root) != before, d
-  before = build.source_hash('valueview', root)
-  with open(os.path.join(root, 'stackrl_amd', 'csrc', 'compare.hip'), 'ab') as f:
-    f.write(b'\n')
-  assert build.source_hash('valueview', root) == before
 
 
 def test_the_table_is_matplotlibs():
@@ -172,13 +83,3 @@ def test_each_refusal_has_its_own_text_and_launches_nothing():
   assert 'frames 0' in refused(P=1, maps=(1,) + (None,) * 7, frames=None)
   assert len(set(texts.values())) == len(texts)
   assert len({t.split(',')[0] for t in texts.values()}) >= 12
-
-
-def test_no_kernel_of_the_library_contains_the_flagged_packed_form():
-  text = build.device_asm(HIPCC, build.QFLAGS, SOURCE)
-  assert not isa_fix.flagged(text)
-  assert 'k_value_range' in text and 'k_value_frame' in text and text.count('v_div_fixup_f32') >= 1     # the scan saw the kernels
-  build.build()
-  texts = isa_fix.shipped_asm(build.VLIB)
-  assert len(texts) == 1 and not isa_fix.flagged(texts[0])
-  assert 'k_value_range' in texts[0] and 'k_value_frame' in texts[0] and texts[0].count('v_div_fixup_f32') >= 1

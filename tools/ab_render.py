@@ -10,7 +10,7 @@ sys.path.insert(0, ROOT)
 from stackrl_amd import build as B
 
 def run(so):
-  B.library('env').path = so
+  B.LIBRARIES['env'].path = so
   import numpy as np, torch
   from stackrl_amd import assets, env as envs
   nB = 1024

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Registers, spills, scratch and instruction count of every kernel of a library, from its compiled device assembly.
 
-usage: kernel_resources.py [env|qnet|compare|rocks] [--dump DIR]
+usage: kernel_resources.py [env|qnet|compare|rocks|valueview|candidates] [--dump DIR]
 
-The library's sources are compiled to gfx950 assembly with its own flags (build.library, build.device_asm); the env library's
+The library's sources are compiled to gfx950 assembly with its own flags (build.LIBRARIES, build.device_asm); the env library's
 text then goes through isa_fix.rewrite, as in the product build.  No GPU needed.  With --dump every kernel's instruction text
 (from its label to its end, labels renumbered in order of appearance) is written to DIR/<kernel>.s, so that two commits can be
 compared with diff: a kernel whose text is the same runs the same instructions."""
@@ -54,7 +54,7 @@ def main(argv):
   if '--dump' in argv:
     i = argv.index('--dump'); dump = argv[i + 1]; argv = argv[:i] + argv[i + 2:]
   name = argv[0] if argv else 'env'
-  lib = build.library(name)
+  lib = build.LIBRARIES[name]
   hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
   if dump:
     os.makedirs(dump, exist_ok=True)

@@ -9,7 +9,7 @@ from stackrl_amd import build as B
 so = os.path.join(ROOT, 'gpurun_out', 'libstackrl_stamps.so')
 os.makedirs(os.path.dirname(so), exist_ok=True)
 subprocess.check_call(['/opt/rocm/bin/hipcc'] + B.FLAGS + ['-DSRL_STAMPS', os.path.join(B.CSRC, 'stackrl_hip.hip'), '-o', so])
-B.library('env').path = so
+B.LIBRARIES['env'].path = so
 import torch
 from stackrl_amd import assets, env as envs, lib
 pool = assets.default_pool()
