@@ -50,8 +50,28 @@ __device__ __forceinline__ void srl_jitter_sync() {
 #define __syncthreads() srl_jitter_sync()
 #endif
 
-// what distinguishes the four kernel variants <threads per env, pair points per thread>: defined beside their entry points
-template <int T, int PP> struct Variant;
+// What a kernel variant <T threads per env, PP pair points per thread> chooses besides those two, each with its measured reason
+// (substep and solver_sweep read these; the entry points with their launch bounds are at the end of the file, the host's row
+// of a variant is k_step_variants, stackrl_hip.hip):
+template <int T, int PP>
+struct Variant {
+  // lanes per manifold slot in the narrow phase: 32 in the 128-thread variant of <= 8 rocks, 16 where there are more slots than
+  // groups (round 5, same box: 1,024 x 16 +1.6 %, 4,096 x 16 +2 %, the headline shape indifferent; bit-identical either way)
+  static constexpr int GJK_GROUP = T == 128 && PP == 1 ? 32 : 16;
+  // the ground phase by body lanes (ground_body) in every variant but the four-wave one with one point per thread (9 - 16
+  // rocks, small batches): built for three waves per SIMD (168 VGPRs) it spills 185 registers with it against 113 and loses
+  // 9 % (1,024 / 2,048 envs x 16 rocks); the others gain 3 - 5 % (profiles/r05_ground_body_ab.txt)
+  static constexpr bool GROUND_BODY = !(T == 256 && PP == 1);
+  // the next ground point's record requested a point ahead (ground_body<AHEAD>): where the variant has the registers
+  static constexpr bool GROUND_AHEAD = T == 128 && PP == 1;
+  // sweeps by wave 0 alone while it holds every contact point (solver_sweep<SOLO>): the variants with two points per thread
+  // are out of registers as it is
+  static constexpr bool SOLO = PP == 1;
+  // a pair contact solved on two lanes, one per body (pair_phase), in the two-wave variant of <= 8 rocks: a launch there lasts
+  // as long as one wave's dependent chain, and a turn is 67 -> 45 vector instructions — 9.42 -> 8.22 ms per launch at the
+  // headline shape; the other three are throughput-bound and out of registers (profiles/pair_split_experiment.md)
+  static constexpr bool PAIR_SPLIT = T == 128 && PP == 1;
+};
 
 // Bodies (i < j) of pair id p = j (j - 1) / 2 + i, computed when the kernel fills its LDS table.  (Until round 3 this
 // was a pair of process-wide __constant__ tables that every srl_create rewrote: device state shared by all handles.)
@@ -158,7 +178,7 @@ __device__ void goal_from_rng(const DevParams& P, uint32_t key, uint32_t episode
   rect[2] = h; rect[3] = w;
 }
 
-__device__ void env_reset(const DevParams& P, EnvHdr* h, int e) {
+__device__ __attribute__((noinline)) void env_reset(const DevParams& P, EnvHdr* h, int e) {
   int L = P.c.episode_length;
   uint32_t key = P.seed + (uint32_t)P.c.env_index_offset + (uint32_t)e;   // utils.py:433
   h->episode += 1;
@@ -403,6 +423,74 @@ __device__ __forceinline__ void sat_faces(const DevParams& P, int mesh_a, const 
   dist = best;
 }
 
+// ------------------------------------------------------------------ diagnostic build (SRL_STAMPS): where a sub-step's time goes
+// EnvHdr::stamps[k]: thread 0's wall-clock ticks from the sub-step's previous stamp to STAMP(k), summed over the env's sub-steps
+// (srl_debug_stamps).  The phases substep stamps, in this order:
+enum { ST_FRAME = 0, ST_VERTS, ST_BOUNDS_GROUND, ST_BROADPHASE, ST_NARROWPHASE, ST_POINT_SETUP, ST_SOLVER, ST_INTEGRATE };
+#ifdef SRL_STAMPS
+#define STAMP_BEGIN long long _t0 = wall_clock64()
+#define STAMP(k) do { if (tid == 0) { long long _t = wall_clock64(); L.P->hdr[blockIdx.x].stamps[k] += _t - _t0; _t0 = _t; } } while (0)
+// EnvHdr::stamps2: thread 0's ticks in slot 0's manifold refresh, GJK and manifold insert, and the calls counted
+struct NarrowClock {
+  long long t0, t1, t3;
+  __device__ __forceinline__ NarrowClock() : t0(wall_clock64()), t1(0), t3(0) {}
+  __device__ __forceinline__ void lap() { t1 = wall_clock64(); }
+  __device__ __forceinline__ void refresh_and_gjk(const Lds& L) {
+    if (threadIdx.x == 0) {
+      const long long t2 = wall_clock64();
+      EnvHdr* hh = &L.P->hdr[blockIdx.x];
+      hh->stamps2[0] += t1 - t0; hh->stamps2[1] += t2 - t1; hh->stamps2[3] += 1;
+    }
+    t3 = wall_clock64();
+  }
+  __device__ __forceinline__ void insert(const Lds& L) {
+    if (threadIdx.x == 0) L.P->hdr[blockIdx.x].stamps2[2] += wall_clock64() - t3;
+  }
+};
+// EnvHdr::diag (srl_debug_diag), by thread 0 after a sub-step's sweeps: sub-steps, of those without a pair point on lane 0,
+// colours, solo sweeps, and the pair turns of a sweep as scheduled (sum over colours of the fullest manifold) and as the
+// longest dependency chain
+__device__ __forceinline__ void sweep_diag(const Lds& L, int tid, int ncol, bool anyp, bool solo) {
+  if (tid == 0) {
+    EnvHdr* hh = &L.P->hdr[blockIdx.x];
+    int bl[SRL_MAX_BODIES]; for (int b = 0; b < SRL_MAX_BODIES; ++b) bl[b] = 0;
+    int lmax = 0, sumt = 0;
+    for (int c = 0; c < ncol; ++c) {
+      int mx = 0;
+      for (int sl = 0; sl < L.P->NS; ++sl) {
+        const int pid = L.POS()[sl];
+        if (pid < 0 || L.COL()[sl] != c) continue;
+        const int np = __float_as_int(L.MAN(sl)[0]);
+        if (np <= 0) continue;
+        int a, b; L.pair(pid, a, b);
+        const int st = bl[a] > bl[b] ? bl[a] : bl[b];
+        bl[a] = st + np; bl[b] = st + np;
+        if (st + np > lmax) lmax = st + np;
+        if (np > mx) mx = np;
+      }
+      sumt += mx;
+    }
+    hh->diag[4] += sumt; hh->diag[5] += lmax;
+    hh->diag[0] += 1; hh->diag[1] += (__ballot(anyp) == 0ull); hh->diag[2] += ncol; hh->diag[3] += solo ? L.MISC()[M_CNT] : 0;
+  }
+}
+// which CU / SIMD the env's first two waves run on (HW_REG_HW_ID = 4, HW_REG_XCC_ID = 20)
+__device__ __forceinline__ void stamp_hw_id(EnvHdr* h) {
+  if ((threadIdx.x & 63) == 0 && threadIdx.x < 128)
+    h->hwid[threadIdx.x >> 6] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
+}
+#else
+#define STAMP_BEGIN
+#define STAMP(k)
+struct NarrowClock {
+  __device__ __forceinline__ void lap() {}
+  __device__ __forceinline__ void refresh_and_gjk(const Lds&) {}
+  __device__ __forceinline__ void insert(const Lds&) {}
+};
+__device__ __forceinline__ void sweep_diag(const Lds&, int, int, bool, bool) {}
+__device__ __forceinline__ void stamp_hw_id(EnvHdr*) {}
+#endif
+
 // G lanes per slot (Variant::GJK_GROUP): GJK runs in lock step on all of them (support scans split), the first lane maintains
 // the manifold
 template <int G>
@@ -418,22 +506,15 @@ __device__ __forceinline__ void narrowphase_slot(const Lds& L, int sl, int gl) {
   float thr = 0.02f * fminf(bca[4], bcb[4]);
   v3 xa = ld3(L.X(a)), xb = ld3(L.X(b));
   m3 Ra = ldm(L.R(a)), Rb = ldm(L.R(b));
-#ifdef SRL_STAMPS
-  long long _n0 = wall_clock64();
-#endif
+  NarrowClock clk;
   if (gl == 0) manifold_refresh(mp, xa, Ra, xb, Rb, thr);
-#ifdef SRL_STAMPS
-  long long _n1 = wall_clock64();
-#endif
+  clk.lap();
   v3 axis = ld3(mp + 1);
   v3 pa, pb, n; float d;
   int cache[3];
   cache[0] = __float_as_int(mp[56]); cache[1] = __float_as_int(mp[57]); cache[2] = __float_as_int(mp[58]);
   int rc = gjk_distance<G>(L.WV(a), na, L.WV(b), nb, axis, cache, (mg + mg) + thr, pa, pb, n, d, gl);
-#ifdef SRL_STAMPS
-  if (threadIdx.x == 0) { long long _n2 = wall_clock64(); EnvHdr* hh = &L.P->hdr[blockIdx.x]; hh->stamps2[0] += _n1 - _n0; hh->stamps2[1] += _n2 - _n1; hh->stamps2[3] += 1; }
-  long long _n3 = wall_clock64();
-#endif
+  clk.refresh_and_gjk(L);
   if (rc == 2) {   // every lane of the group got the same rc: the face scan is shared
     sat_faces<G>(P, __float_as_int(bca[7]), L.WV(a), na, __float_as_int(bcb[7]), L.WV(b), nb, pa, pb, n, d, gl);
     if (gl != 0) return;
@@ -451,19 +532,10 @@ __device__ __forceinline__ void narrowphase_slot(const Lds& L, int sl, int gl) {
       manifold_add(mp, mtmul(Ra, sa - xa), mtmul(Rb, sb - xb), n, dist, thr);
     }
   }
-#ifdef SRL_STAMPS
-  if (threadIdx.x == 0) { EnvHdr* hh = &L.P->hdr[blockIdx.x]; hh->stamps2[2] += wall_clock64() - _n3; }
-#endif
+  clk.insert(L);
 }
 
 #include "solver.h"   // sequential impulses: rows, both ground and both pair formulations, solver_sweep
-
-// ------------------------------------------------------------------ one sub-step (block-wide)
-#ifdef SRL_STAMPS
-#define STAMP(k) do { if (tid == 0) { long long _t = wall_clock64(); L.P->hdr[blockIdx.x].stamps[k] += _t - _t0; _t0 = _t; } } while (0)
-#else
-#define STAMP(k)
-#endif
 
 template <int T, int PP>
 __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gsweep) {
@@ -475,15 +547,13 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
   // The same with the pair split's two register sets per lane: 40 spill stores / reloads and 116 bytes of scratch without
   // it, none with it (the parent had 8 and 68 bytes); the launch time is the same either way (profiles/pair_split_ab.txt).
   if (PP >= 2 || VA::PAIR_SPLIT) asm volatile("" : "+v"(tid));
-#ifdef SRL_STAMPS
-  long long _t0 = wall_clock64();
-#endif
+  STAMP_BEGIN;
   int* misc = L.MISC();
   // (1) lane = body: damping, gravity, frame
   if (tid < nb) body_frame(L, tid);
   if (tid == 0) { misc[M_FLAGS] = 0; misc[M_SOLO] = 1; }
   __syncthreads();
-  STAMP(0);
+  STAMP(ST_FRAME);
   // (2) lane = (body, vertex): world vertices
   for (int it = tid; it < nb * P.VS; it += T) {
     const int b = it / P.VS, k = it - b * P.VS;
@@ -496,11 +566,11 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
     }
   }
   __syncthreads();
-  STAMP(1);
+  STAMP(ST_VERTS);
   // (3) 16 lanes = body: AABB + ground manifold
   for (int b = tid >> 4; b < nb; b += T >> 4) body_bounds_ground(L, b, tid & 15);
   __syncthreads();
-  STAMP(2);
+  STAMP(ST_BOUNDS_GROUND);
   // (4) broadphase: AABB overlap for every pair; release slots of pairs that separated
   const int npair = nb * (nb - 1) / 2;
   int fl = 0;
@@ -552,7 +622,7 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
     __syncthreads();
   }
   const int ncol = misc[M_NCOL];
-  STAMP(3);
+  STAMP(ST_BROADPHASE);
   // (5) narrowphase: G lanes per slot
   {
     constexpr int G = VA::GJK_GROUP;
@@ -561,7 +631,7 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
       if (L.POS()[sl] >= 0) narrowphase_slot<G>(L, sl, gl);
   }
   __syncthreads();
-  STAMP(4);
+  STAMP(ST_NARROWPHASE);
   // (6) sequential impulses: lane = contact point, row constants in registers for all sweeps
   {
     GPoint gp = make_ground_point(L, tid / SRL_GMAXP, tid % SRL_GMAXP);
@@ -603,7 +673,7 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
     __syncthreads();   // the records are in LDS
     }
     if constexpr (VA::PAIR_SPLIT) sp = make_pair_split(L, tid);
-    STAMP(5);
+    STAMP(ST_POINT_SETUP);
     const bool solo = VA::SOLO && misc[M_SOLO] != 0;
     // the ground points' friction coefficient, made here once and kept as a scalar (not loaded and multiplied in every sweep)
     const float gmu = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ground_mu(P.c))));
@@ -665,34 +735,12 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
         if (!solver_sweep<false, T, PP, false>(L, gp, gb, pp, sp, ncol, gslot, pslot, gsweep, cm, cm2, gmu)) break;
       }
     }
-#ifdef SRL_STAMPS
-    if (tid == 0) {
-      EnvHdr* hh = &L.P->hdr[blockIdx.x];
+    {   // (diagnostic build; sweep_diag is empty otherwise)
       bool anyp = false;
+#pragma unroll
       for (int r = 0; r < PP; ++r) anyp |= pp[r].valid;
-      {   // pair turns of a sweep as scheduled (sum over colours of the fullest manifold) and as the longest dependency chain
-        int bl[SRL_MAX_BODIES]; for (int b = 0; b < SRL_MAX_BODIES; ++b) bl[b] = 0;
-        int lmax = 0, sumt = 0;
-        for (int c = 0; c < ncol; ++c) {
-          int mx = 0;
-          for (int sl = 0; sl < P.NS; ++sl) {
-            const int pid = L.POS()[sl];
-            if (pid < 0 || L.COL()[sl] != c) continue;
-            const int np = __float_as_int(L.MAN(sl)[0]);
-            if (np <= 0) continue;
-            int a, b; L.pair(pid, a, b);
-            const int st = bl[a] > bl[b] ? bl[a] : bl[b];
-            bl[a] = st + np; bl[b] = st + np;
-            if (st + np > lmax) lmax = st + np;
-            if (np > mx) mx = np;
-          }
-          sumt += mx;
-        }
-        hh->diag[4] += sumt; hh->diag[5] += lmax;
-      }
-      hh->diag[0] += 1; hh->diag[1] += (__ballot(anyp) == 0ull); hh->diag[2] += ncol; hh->diag[3] += solo ? misc[M_CNT] : 0;
+      sweep_diag(L, tid, ncol, anyp, solo);
     }
-#endif
     // accumulated impulses back to the manifolds (warm start of the next sub-step)
     if (!GB) {
       if (gp.valid) { float* g = L.GM(gp.a); g[SRL_GM_IN + gp.idx] = gp.in; g[SRL_GM_T1 + gp.idx] = gp.i1; g[SRL_GM_T2 + gp.idx] = gp.i2; }
@@ -718,7 +766,7 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
       }
     }
   }
-  STAMP(6);
+  STAMP(ST_SOLVER);
   // (7) integrate (the last solver phase ended with a barrier)
   const float dt = P.c.sim_time_step;
   if (tid < nb) {
@@ -739,7 +787,7 @@ __device__ __forceinline__ void substep(const Lds& L, int nb, int tid, int& gswe
     Q[0] = q.x * inv; Q[1] = q.y * inv; Q[2] = q.z * inv; Q[3] = q.w * inv;
   }
   __syncthreads();
-  STAMP(7);
+  STAMP(ST_INTEGRATE);
 }
 
 // simulator.py:322-335: every body's linear speed <= threshold
@@ -834,7 +882,192 @@ __device__ __attribute__((noinline)) void stage_tail(const DevParams* __restrict
   }
 }
 
-// ------------------------------------------------------------------ K1 + K4 + episode machine
+// ------------------------------------------------------------------ K1 + K4 + episode machine: the phases of a call, then step_body
+// what a call does to an env (EnvHdr::mode, M_MODE): decode_call decides
+enum { CALL_PLACE = 0, CALL_RESET = 1, CALL_REJECTED = 2, CALL_HOLD = 3, CALL_RAW = 4 };
+
+// Thread 0: the episode machine.  Decides what the call does to env e, advances the episode's rock list, and leaves the words
+// the other phases read in LDS (M_MODE; placement: M_U, M_V, M_ORIENT, M_PENDING, M_NEXT; with sub-steps: M_NB, M_NCOL, M_STATUS).
+__device__ __forceinline__ void decode_call(const DevParams& P, const Lds& L, EnvHdr* h, int e, const int64_t* __restrict__ action,
+                                            int force_reset) {
+  int* misc = L.MISC();
+  int mode;
+  if (force_reset < 0) {                    // srl_step_simulation: -force_reset raw sub-steps, no placement
+    mode = h->nb > 0 ? CALL_RAW : CALL_HOLD;
+    misc[M_NB] = h->nb;
+    misc[M_NCOL] = h->ncolour;
+    misc[M_STATUS] = h->status;
+    misc[M_RES0] = -1; misc[M_RES1] = -1;
+  } else if (!force_reset && action[e] == (int64_t)SRL_ACTION_HOLD) {
+    mode = CALL_HOLD;                       // this env sits the call out (srl_types.h)
+  } else if (force_reset || h->done) {     // env.py:235-236 auto-reset
+    env_reset(P, h, e);
+    mode = CALL_RESET;
+  } else {
+    int64_t a = action[e];
+    int oi = 0, slot = 0;                   // TestStackEnv: action = (observation index, pixel), env.py:485-494
+    if (P.n_slots > 1 && a >= 0) {
+      // the index addresses the object maps on show: n_orient of the pending rock, or n_orient of every unplaced rock
+      const int nvalid = P.c.ordering_freedom ? h->list_pos * P.n_orient : P.n_orient;
+      slot = (int)(a / (int64_t)P.A);
+      a = slot < nvalid ? a % (int64_t)P.A : -1;
+      oi = slot % P.n_orient;
+    }
+    misc[M_ORIENT] = oi;
+    if (a < 0 || a >= (int64_t)P.A) {       // env.py:238
+      h->status |= SRL_ST_BAD_ACTION;
+      atomicOr(P.flags, 1);
+      mode = CALL_REJECTED;
+    } else {
+      h->status &= ~SRL_ST_BAD_ACTION;
+      mode = CALL_PLACE;
+      misc[M_U] = (int)(a / P.AW);          // env.py:240-241
+      misc[M_V] = (int)(a % P.AW);
+      int next = -1, placed = h->pending;
+      if (P.c.ordering_freedom) {           // TestSimulator.step: pop the chosen rock (simulator.py:372-378)
+        const int rk = slot / P.n_orient;
+        placed = h->ids[rk];
+        for (int k = rk; k + 1 < h->list_pos; ++k) h->ids[k] = h->ids[k + 1];
+        h->list_pos -= 1;
+        if (h->list_pos == 0) h->done = 1;  // env.py:513-514: no objects left
+        else next = h->ids[0];
+      } else if (h->list_pos < P.c.episode_length) next = h->ids[h->list_pos++];   // env.py:243-247
+      else h->done = 1;
+      misc[M_NEXT] = next;
+      misc[M_NB] = h->nb;
+      misc[M_PENDING] = placed;
+      misc[M_NCOL] = h->ncolour;
+      misc[M_STATUS] = h->status;
+      misc[M_ZMAX] = (int)f2o(-1e30f);
+      misc[M_RES0] = -1; misc[M_RES1] = -1;
+    }
+  }
+  h->mode = mode;
+  misc[M_MODE] = mode;
+}
+
+// Simulator.reset: empty world (simulator.py:156-188)
+template <int T>
+__device__ __forceinline__ void reset_world(const DevParams& P, float* gblob, int tid) {
+  int* gi = (int*)gblob;
+  for (int k = tid; k < P.NP; k += T) gi[P.OFF_SOP + k] = -1;
+  for (int k = tid; k < P.NS; k += T) gi[P.OFF_POS + k] = -1;
+}
+
+// the persistent blob into LDS, and the table of the pairs' bodies beside it
+template <int T>
+__device__ __forceinline__ void load_blob(const Lds& L, const float* gblob, int tid) {
+  for (int k = tid; k < L.P->BLOB; k += T) L.sm[k] = gblob[k];
+  for (int k = tid; k < L.P->NP; k += T) L.PAIR()[k] = pair_word(k);
+}
+
+// K4: Observer.pose (observer.py:392-421): z = max(H[window] + O | O > 1e-4) - oz/2; the maximum to M_ZMAX
+template <int T>
+__device__ __forceinline__ void release_height(const Lds& L, int e, int tid, int u, int v, int pending) {
+  const DevParams& P = *L.P;
+  int* misc = L.MISC();
+  const int res = P.c.overhead_res, r = P.c.object_res;
+  const float* Hm = P.H + (size_t)e * res * res;
+  const float* Om = P.objmap + ((size_t)pending * P.n_orient + misc[M_ORIENT]) * r * r;
+  uint32_t best = f2o(-1e30f);
+  for (int k = tid; k < r * r; k += T) {
+    int i = k / r, j = k % r;
+    float o = Om[k];
+    if (o > 1e-4f) {
+      uint32_t s = f2o(Hm[(u + i) * res + (v + j)] + o);
+      best = s > best ? s : best;
+    }
+  }
+  atomicMax((uint32_t*)&misc[M_ZMAX], best);
+}
+
+// Thread 0: _place (simulator.py:310-320): teleport the pending rock, as body b, to the release pose, zero velocity
+__device__ __forceinline__ void place_rock(const Lds& L, int b, int u, int v, int pending) {
+  const DevParams& P = *L.P;
+  int* misc = L.MISC();
+  float z = o2f((uint32_t)misc[M_ZMAX]);
+  float half = ((float)P.c.object_res * P.px) * 0.5f;
+  v3 pos = V((float)u * P.px + half, (float)v * P.px + half, z - half);
+  const MeshHdr mh = P.mh[pending];
+  L.MESH()[b] = pending;
+  // resetBasePositionAndOrientation moves the inertial (COM) frame; loadURDF had placed the link frame
+  if (P.n_orient == 1) {
+    st3(L.X(b), P.c.place_at_com ? pos : pos + V(mh.cx, mh.cy, mh.cz));
+    L.Q(b)[0] = 0.0f; L.Q(b)[1] = 0.0f; L.Q(b)[2] = 0.0f; L.Q(b)[3] = 1.0f;
+  } else {   // the chosen orientation (observer.py:416-417 -> simulator.py:313)
+    const float* oq = P.orient_q[misc[M_ORIENT]];
+    q4 q; q.x = oq[0]; q.y = oq[1]; q.z = oq[2]; q.w = oq[3];
+    st3(L.X(b), P.c.place_at_com ? pos : pos + mmul(quat_to_mat(q), V(mh.cx, mh.cy, mh.cz)));
+    L.Q(b)[0] = q.x; L.Q(b)[1] = q.y; L.Q(b)[2] = q.z; L.Q(b)[3] = q.w;
+  }
+  vw_store(L.VW(b), V(0, 0, 0), V(0, 0, 0));
+  L.GM(b)[0] = __int_as_float(0);
+}
+
+// lane = body: what the sub-steps read of a body's mesh (Lds::BC)
+template <int T>
+__device__ __forceinline__ void body_constants(const Lds& L, int nb, int tid) {
+  for (int b = tid; b < nb; b += T) {
+    int m = L.MESH()[b];
+    const MeshHdr mh = L.P->mh[m];
+    float* bc = L.BC(b);
+    bc[0] = mh.inv_mass; bc[1] = mh.iix; bc[2] = mh.iiy; bc[3] = mh.iiz; bc[4] = mh.radius;
+    bc[5] = __int_as_float(mh.nv); bc[6] = __int_as_float(mh.vo); bc[7] = __int_as_float(m);
+  }
+}
+
+// local (COM-frame) vertices of every body into LDS, once per step (the 32-rock variant reads them from the mesh table
+// instead: without this copy two of its workgroups fit a CU)
+template <int T>
+__device__ __forceinline__ void local_vertices(const Lds& L, int nb, int tid) {
+  const DevParams& P = *L.P;
+  if (P.S_LV >= 0)
+    for (int it = tid; it < nb * P.VS; it += T) {
+      const int b = it / P.VS, k = it - b * P.VS;
+      const float* bc = L.BC(b);
+      if (k < __float_as_int(bc[5])) {
+        float4 lv = P.mv[__float_as_int(bc[6]) + k];
+        st3(L.LV(b) + 3 * k, V(lv.x, lv.y, lv.z));
+      }
+    }
+}
+
+// settle_loop, SMOOTH: left at _drop (three contact points on the newest body, simulator.py:337-341) or at _stop
+template <int T>
+__device__ __forceinline__ bool smooth_ends(const Lds& L, int nb, int tid) {
+  const bool drop = newest_contacts(L, nb, tid, T) >= 3;
+  const bool stop = sim_stop(L, nb, tid);
+  return drop || stop;
+}
+
+// settle_loop, ENTER: thread 0 keeps the pose where the rock was left (simulator.py:227-230)
+__device__ __forceinline__ void keep_place_pose(const Lds& L, int b) {
+  st3(L.PX(b), ld3(L.X(b)));
+  for (int k = 0; k < 4; ++k) L.PQ(b)[k] = L.Q(b)[k];
+}
+
+// the blob back to the env's global copy, and by thread 0 the header words the sub-steps moved; after a placement (counter
+// sub-steps, s_a of them before the drop, `diverged`: ended by the cap) also the body count, the next rock (_load,
+// simulator.py:258) and the sub-step counts
+template <int T>
+__device__ __forceinline__ void write_back(const Lds& L, EnvHdr* h, float* gblob, int tid, int gsweep, bool placement, int nb,
+                                           int counter, int s_a, bool diverged) {
+  int* misc = L.MISC();
+  for (int k = tid; k < L.P->BLOB; k += T) gblob[k] = L.sm[k];
+  if (tid == 0) {
+    if (placement) {
+      h->nb = nb;
+      h->pending = misc[M_NEXT];
+      h->substeps[0] = s_a;
+      h->substeps[1] = counter - s_a;
+    }
+    h->ncolour = misc[M_NCOL];
+    h->sweeps = gsweep;
+    h->status = misc[M_STATUS] | (diverged ? SRL_ST_DIVERGED : 0);
+    if (diverged) atomicOr(L.P->flags, 2);
+  }
+}
+
 // Pp points to the handle's DevParams in device memory: every field access is a scalar load.  (A by-value
 // kernel argument whose address is taken is copied to scratch and every access becomes a scratch load.)
 template <int T, int PP>
@@ -849,157 +1082,41 @@ __device__ __forceinline__ void step_body(const DevParams* __restrict__ Pp, cons
   int* misc = L.MISC();
   EnvHdr* h = &P.hdr[e];
   float* gblob = P.blob + (size_t)e * P.BLOB;
-#ifdef SRL_STAMPS
-  if ((threadIdx.x & 63) == 0 && threadIdx.x < 128)   // which CU / SIMD the env's waves run on (HW_REG_HW_ID = 4, HW_REG_XCC_ID = 20)
-    h->hwid[threadIdx.x >> 6] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
-#endif
-
-  if (tid == 0) {
-    int mode;
-    if (force_reset < 0) {                    // srl_step_simulation: -force_reset raw sub-steps, no placement
-      mode = h->nb > 0 ? 4 : 3;
-      misc[M_NB] = h->nb;
-      misc[M_NCOL] = h->ncolour;
-      misc[M_STATUS] = h->status;
-      misc[M_RES0] = -1; misc[M_RES1] = -1;
-    } else if (!force_reset && action[e] == (int64_t)SRL_ACTION_HOLD) {
-      mode = 3;                               // this env sits the call out (srl_types.h)
-    } else if (force_reset || h->done) {     // env.py:235-236 auto-reset
-      env_reset(P, h, e);
-      mode = 1;
-    } else {
-      int64_t a = action[e];
-      int oi = 0, slot = 0;                   // TestStackEnv: action = (observation index, pixel), env.py:485-494
-      if (P.n_slots > 1 && a >= 0) {
-        // the index addresses the object maps on show: n_orient of the pending rock, or n_orient of every unplaced rock
-        const int nvalid = P.c.ordering_freedom ? h->list_pos * P.n_orient : P.n_orient;
-        slot = (int)(a / (int64_t)P.A);
-        a = slot < nvalid ? a % (int64_t)P.A : -1;
-        oi = slot % P.n_orient;
-      }
-      misc[M_ORIENT] = oi;
-      if (a < 0 || a >= (int64_t)P.A) {       // env.py:238
-        h->status |= SRL_ST_BAD_ACTION;
-        atomicOr(P.flags, 1);
-        mode = 2;
-      } else {
-        h->status &= ~SRL_ST_BAD_ACTION;
-        mode = 0;
-        misc[M_U] = (int)(a / P.AW);          // env.py:240-241
-        misc[M_V] = (int)(a % P.AW);
-        int next = -1, placed = h->pending;
-        if (P.c.ordering_freedom) {           // TestSimulator.step: pop the chosen rock (simulator.py:372-378)
-          const int rk = slot / P.n_orient;
-          placed = h->ids[rk];
-          for (int k = rk; k + 1 < h->list_pos; ++k) h->ids[k] = h->ids[k + 1];
-          h->list_pos -= 1;
-          if (h->list_pos == 0) h->done = 1;  // env.py:513-514: no objects left
-          else next = h->ids[0];
-        } else if (h->list_pos < P.c.episode_length) next = h->ids[h->list_pos++];   // env.py:243-247
-        else h->done = 1;
-        misc[M_NEXT] = next;
-        misc[M_NB] = h->nb;
-        misc[M_PENDING] = placed;
-        misc[M_NCOL] = h->ncolour;
-        misc[M_STATUS] = h->status;
-        misc[M_ZMAX] = (int)f2o(-1e30f);
-        misc[M_RES0] = -1; misc[M_RES1] = -1;
-      }
-    }
-    h->mode = mode;
-    misc[M_MODE] = mode;
-  }
+  stamp_hw_id(h);
+  if (tid == 0) decode_call(P, L, h, e, action, force_reset);
   __syncthreads();
   const int mode = misc[M_MODE];
-  if (mode == 1) {   // Simulator.reset: empty world (simulator.py:156-188)
-    int* gi = (int*)gblob;
-    for (int k = tid; k < P.NP; k += T) gi[P.OFF_SOP + k] = -1;
-    for (int k = tid; k < P.NS; k += T) gi[P.OFF_POS + k] = -1;
-    return;
-  }
-  if (mode == 2 || mode == 3) return;
-
-  // ---- load the persistent blob into LDS
-  for (int k = tid; k < P.BLOB; k += T) sm[k] = gblob[k];
-  for (int k = tid; k < P.NP; k += T) L.PAIR()[k] = pair_word(k);
+  if (mode == CALL_RESET) { reset_world<T>(P, gblob, tid); return; }
+  if (mode == CALL_REJECTED || mode == CALL_HOLD) return;
+  load_blob<T>(L, gblob, tid);
   __syncthreads();
-
-  // ---- K4: Observer.pose (observer.py:392-421): z = max(H[window] + O | O > 1e-4) - oz/2
   const int u = misc[M_U], v = misc[M_V], pending = misc[M_PENDING];
   int nb = misc[M_NB];
-  if (mode == 0) {
-    const int res = P.c.overhead_res, r = P.c.object_res;
-    const float* Hm = P.H + (size_t)e * res * res;
-    const float* Om = P.objmap + ((size_t)pending * P.n_orient + misc[M_ORIENT]) * r * r;
-    uint32_t best = f2o(-1e30f);
-    for (int k = tid; k < r * r; k += T) {
-      int i = k / r, j = k % r;
-      float o = Om[k];
-      if (o > 1e-4f) {
-        uint32_t s = f2o(Hm[(u + i) * res + (v + j)] + o);
-        best = s > best ? s : best;
-      }
-    }
-    atomicMax((uint32_t*)&misc[M_ZMAX], best);
-  }
+  if (mode == CALL_PLACE) release_height<T>(L, e, tid, u, v, pending);
   __syncthreads();
-  if (tid == 0 && mode == 0) {   // _place (simulator.py:310-320): teleport the pending rock, zero velocity
-    float z = o2f((uint32_t)misc[M_ZMAX]);
-    float half = ((float)P.c.object_res * P.px) * 0.5f;
-    v3 pos = V((float)u * P.px + half, (float)v * P.px + half, z - half);
-    const MeshHdr mh = P.mh[pending];
-    int b = nb;
-    L.MESH()[b] = pending;
-    // resetBasePositionAndOrientation moves the inertial (COM) frame; loadURDF had placed the link frame
-    if (P.n_orient == 1) {
-      st3(L.X(b), P.c.place_at_com ? pos : pos + V(mh.cx, mh.cy, mh.cz));
-      L.Q(b)[0] = 0.0f; L.Q(b)[1] = 0.0f; L.Q(b)[2] = 0.0f; L.Q(b)[3] = 1.0f;
-    } else {   // the chosen orientation (observer.py:416-417 -> simulator.py:313)
-      const float* oq = P.orient_q[misc[M_ORIENT]];
-      q4 q; q.x = oq[0]; q.y = oq[1]; q.z = oq[2]; q.w = oq[3];
-      st3(L.X(b), P.c.place_at_com ? pos : pos + mmul(quat_to_mat(q), V(mh.cx, mh.cy, mh.cz)));
-      L.Q(b)[0] = q.x; L.Q(b)[1] = q.y; L.Q(b)[2] = q.z; L.Q(b)[3] = q.w;
-    }
-    vw_store(L.VW(b), V(0, 0, 0), V(0, 0, 0));
-    L.GM(b)[0] = __int_as_float(0);
-  }
-  if (mode == 0) nb += 1;
+  if (tid == 0 && mode == CALL_PLACE) place_rock(L, nb, u, v, pending);
+  if (mode == CALL_PLACE) nb += 1;
   __syncthreads();
-  for (int b = tid; b < nb; b += T) {
-    int m = L.MESH()[b];
-    const MeshHdr mh = P.mh[m];
-    float* bc = L.BC(b);
-    bc[0] = mh.inv_mass; bc[1] = mh.iix; bc[2] = mh.iiy; bc[3] = mh.iiz; bc[4] = mh.radius;
-    bc[5] = __int_as_float(mh.nv); bc[6] = __int_as_float(mh.vo); bc[7] = __int_as_float(m);
-  }
+  body_constants<T>(L, nb, tid);
   __syncthreads();
-  // local (COM-frame) vertices of every body into LDS, once per step (the 32-rock variant reads them from the mesh table
-  // instead: without this copy two of its workgroups fit a CU)
-  if (P.S_LV >= 0)
-  for (int it = tid; it < nb * P.VS; it += T) {
-    const int b = it / P.VS, k = it - b * P.VS;
-    const float* bc = L.BC(b);
-    if (k < __float_as_int(bc[5])) {
-      float4 lv = P.mv[__float_as_int(bc[6]) + k];
-      st3(L.LV(b) + 3 * k, V(lv.x, lv.y, lv.z));
-    }
-  }
+  local_vertices<T>(L, nb, tid);
   __syncthreads();
-
-  // ---- Simulator.step (simulator.py:190-258) as one loop around a single sub-step call site:
+  int gsweep = 0;   // solver sweeps of this launch (block-uniform); the residual words start at -1
+  if (mode == CALL_RAW) {   // stepSimulation x n (srl_step_simulation): no placement, no stop criterion, no render records
+    for (int k = 0; k < -force_reset; ++k) substep<T, PP>(L, nb, tid, gsweep);
+    write_back<T>(L, h, gblob, tid, gsweep, false, nb, 0, 0, false);
+    return;
+  }
+  // settle_loop: Simulator.step (simulator.py:190-258) as one loop around a single sub-step call site.
   //   PLACE  : the sub-step of _place (simulator.py:320)
   //   SMOOTH : "zero the newest body's velocity, step" until _drop (simulator.py:212-224)
   //   SETTLE : step until _stop (simulator.py:239-245)
+  // (The loop stands here, not in a phase of its own: as a function that hands counter, s_a and diverged back it moved
+  //  srl_k_step_pp1 from 101 spilled registers and 404 bytes of scratch to 99 and 420.  The SMOOTH test keeps its nested form
+  //  for the same reason: as one `&& (diverged || ...)` condition it cost that kernel a spilled register.)
   enum { PH_PLACE = 0, PH_SMOOTH = 1, PH_ENTER = 2, PH_SETTLE = 3 };
   int counter = 0, phase = PH_PLACE, s_a = 0;
-  int gsweep = 0;   // solver sweeps of this launch (block-uniform); the residual words start at -1
   bool diverged = false;
-  if (mode == 4) {   // stepSimulation x n (srl_step_simulation): no placement, no stop criterion
-    for (int k = 0; k < -force_reset; ++k) substep<T, PP>(L, nb, tid, gsweep);
-    for (int k = tid; k < P.BLOB; k += T) gblob[k] = sm[k];
-    if (tid == 0) { h->ncolour = misc[M_NCOL]; h->status = misc[M_STATUS]; h->sweeps = gsweep; }
-    return;
-  }
   for (;;) {
     if (phase == PH_SMOOTH) {
       if (tid == 0) vw_store(L.VW(nb - 1), V(0, 0, 0), V(0, 0, 0));   // resetBaseVelocity
@@ -1011,40 +1128,19 @@ __device__ __forceinline__ void step_body(const DevParams* __restrict__ Pp, cons
     if (phase == PH_PLACE) phase = P.c.smooth_placing ? PH_SMOOTH : PH_ENTER;
     if (phase == PH_SMOOTH) {
       bool leave = diverged;
-      if (!leave) {
-        const bool drop = newest_contacts(L, nb, tid, T) >= 3;   // _drop, simulator.py:337-341
-        const bool stop = sim_stop(L, nb, tid);
-        leave = drop || stop;
-      }
+      if (!leave) leave = smooth_ends<T>(L, nb, tid);
       if (leave) phase = PH_ENTER;
     }
-    if (phase == PH_ENTER) {   // simulator.py:227-230: pose where the rock was left, steps before the drop
-      if (tid == 0 && !diverged) {   // (the reference raises out of the smooth-placing loop at the cap: no place pose then)
-        st3(L.PX(nb - 1), ld3(L.X(nb - 1)));
-        for (int k = 0; k < 4; ++k) L.PQ(nb - 1)[k] = L.Q(nb - 1)[k];
-      }
+    if (phase == PH_ENTER) {   // steps before the drop; no place pose at the cap (the reference raises out of the smooth-placing loop)
+      if (tid == 0 && !diverged) keep_place_pose(L, nb - 1);
       s_a = counter;
       phase = PH_SETTLE;
     }
     if (phase == PH_SETTLE && (diverged || sim_stop(L, nb, tid))) break;
   }
   __syncthreads();
-
-  // ---- write back
-  for (int k = tid; k < P.BLOB; k += T) gblob[k] = sm[k];
-  if (tid == 0) {
-    h->nb = nb;
-    h->pending = misc[M_NEXT];   // _load, simulator.py:258
-    h->ncolour = misc[M_NCOL];
-    h->substeps[0] = s_a;
-    h->substeps[1] = counter - s_a;
-    h->sweeps = gsweep;
-    int st = misc[M_STATUS] | (diverged ? SRL_ST_DIVERGED : 0);
-    h->status = st;
-    if (diverged) atomicOr(P.flags, 2);
-  }
-
-  // ---- the rocks' render records (stage.h), by a function of its own: see stage_tail
+  write_back<T>(L, h, gblob, tid, gsweep, true, nb, counter, s_a, diverged);
+  // the rocks' render records (stage.h), by a function of its own: see stage_tail
   if (stage != nullptr) stage_tail<T>(Pp, stage, e, nb);
 }
 
@@ -1054,29 +1150,8 @@ __device__ __forceinline__ void step_body(const DevParams* __restrict__ Pp, cons
 // kept a slot for every pair up to 16 rocks and 192 above, which needed two points per thread and 256 VGPRs + scratch.)
 // The 16-rock variant is built for three waves per SIMD (168 VGPRs, 62 spilled to scratch): its shapes (2,048 - 4,096
 // envs x 16 rocks) are throughput-bound, and a third workgroup per CU is worth more than the spills cost — 60.7 -> 50.1 ms
-// per launch at 4,096 envs; four waves per SIMD (128 VGPRs) spill 108 registers and lose: 80 ms.
-// What a variant <T, PP> chooses besides its threads and points per thread, each with its measured reason (substep and
-// solver_sweep read these; the host's row of the variant is k_step_variants, stackrl_hip.hip):
-template <int T, int PP>
-struct Variant {
-  // lanes per manifold slot in the narrow phase: 32 in the 128-thread variant of <= 8 rocks, 16 where there are more slots than
-  // groups (round 5, same box: 1,024 x 16 +1.6 %, 4,096 x 16 +2 %, the headline shape indifferent; bit-identical either way)
-  static constexpr int GJK_GROUP = T == 128 && PP == 1 ? 32 : 16;
-  // the ground phase by body lanes (ground_body) in every variant but the four-wave one with one point per thread (9 - 16
-  // rocks, small batches): built for three waves per SIMD (168 VGPRs) it spills 185 registers with it against 113 and loses
-  // 9 % (1,024 / 2,048 envs x 16 rocks); the others gain 3 - 5 % (profiles/r05_ground_body_ab.txt)
-  static constexpr bool GROUND_BODY = !(T == 256 && PP == 1);
-  // the next ground point's record requested a point ahead (ground_body<AHEAD>): where the variant has the registers
-  static constexpr bool GROUND_AHEAD = T == 128 && PP == 1;
-  // sweeps by wave 0 alone while it holds every contact point (solver_sweep<SOLO>): the variants with two points per thread
-  // are out of registers as it is
-  static constexpr bool SOLO = PP == 1;
-  // a pair contact solved on two lanes, one per body (pair_phase), in the two-wave variant of <= 8 rocks: a launch there lasts
-  // as long as one wave's dependent chain, and a turn is 67 -> 45 vector instructions — 9.42 -> 8.22 ms per launch at the
-  // headline shape; the other three are throughput-bound and out of registers (profiles/pair_split_experiment.md)
-  static constexpr bool PAIR_SPLIT = T == 128 && PP == 1;
-};
-
+// per launch at 4,096 envs; four waves per SIMD (128 VGPRs) spill 108 registers and lose: 80 ms.  What else a variant chooses:
+// Variant<T, PP>, at the top of the file.
 extern "C" __global__ void __launch_bounds__(128, 2) srl_k_step(const DevParams* __restrict__ Pp,
     const int64_t* __restrict__ action, int force_reset, const int32_t* __restrict__ order, float4* __restrict__ stage) {
   step_body<128, 1>(Pp, action, force_reset, order, stage);

@@ -22,6 +22,7 @@ for k in range(L):
 out = np.zeros((n, 12), np.int64)
 lib.load().srl_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.load().srl_debug_stamps(g._h, out.ctypes.data_as(ctypes.c_void_p))
+# the sub-step's stamps in the order of settle.hip's enum ST_FRAME ... ST_INTEGRATE (EnvHdr::stamps)
 names = ['frame', 'verts', 'bounds+ground', 'broadphase+colour', 'narrowphase', 'point setup', 'solver', 'integrate']
 per = out[:, :8].sum(0) / tot_sub.sum() * 10.0   # 100 MHz ticks -> ns
 np2 = out[:, 8:].sum(0)
