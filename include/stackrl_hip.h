@@ -212,6 +212,56 @@ int srl_state_set(srl_env* env, uint64_t signature, const int32_t* dst_idx_dev, 
  * restore.  A seed other than the handle's waits for the device first, like srl_seed. */
 int srl_state_set_rng(srl_env* env, uint32_t seed, uint32_t sample_counter);
 
+/* ---- Contact points: `Simulator.contact_points` (simulator.py:131-133, pybullet's getContactPoints; part of
+ * `Simulator.state`, :135-138) of every env, gathered on the device (csrc/contacts.hip).  Nothing is simulated for it: the
+ * manifolds and their accumulated impulses persist in every env's state between steps.  The definition, float32 with one
+ * rounding per written operation; fma, dot as in the camera section, cross(a, b) = (fma(a.y, b.z, -(a.z * b.y)), fma(a.z, b.x,
+ * -(a.x * b.z)), fma(a.x, b.y, -(a.y * b.x))), R . v + x = per row i fma(R_i0, v.x, fma(R_i1, v.y, fma(R_i2, v.z, x_i))), R from
+ * the body's quaternion as the solver makes it:
+ *   order    of an env's contacts: first the ground points, body slot b ascending over b < nb, then point k < np ascending;
+ *            then the pair points, manifold slot ascending over the slots in use, then point k ascending — the enumeration
+ *            of srl_get_contacts, whose n_points is the count here.
+ *   bodies   (a, b) as int32 body slots (the indexes of srl_get_state's poses), b = -1 for the ground.  pybullet's unique
+ *            ids are not imitated: they depend on what else a client created (`draw_rectangle` bodies, the plane).
+ *   row      srl_contact_row_words() = 20 float32 words: position on A xyz, position on B xyz (world coordinates), normal
+ *            on B xyz (world, pointing from B towards A), distance (negative = penetration), normal force, lateral friction
+ *            force 1 and its direction xyz, lateral friction force 2 and its direction xyz, and a word that is 0.
+ *   ground   a = the body, b = -1.  Position on A = x + R . v, v = mesh vertex `vid` of the ground manifold in the body's
+ *            centre-of-mass frame: the world vertex the settle kernel tests against the plane.  Position on B = that point
+ *            dropped to the plane, (A.x, A.y, 0); the ground is the half-space z < 0.  Normal (0, 0, 1); the directions are the
+ *            solver's, btPlaneSpace1 of +z: (0, -1, 0) and (1, -0, -0).  Distance = the manifold's (z of the vertex less the
+ *            collision margin).
+ *   pair     a manifold slot holds bodies i < j and, per point, la, lb, n, dist: la and lb are in the frames of i and j about
+ *            their positions (the narrow phase stores R_i^T (p - x_i)), n is in world coordinates and points from j towards i
+ *            (GJK's axis a - b; a positive normal impulse moves i along +n).  That is pybullet's convention with A = i, B = j,
+ *            so a = i, b = j: neither swapped nor negated.  Position on A = x_i + R_i . la, on B = x_j + R_j . lb: the current
+ *            pose applied to the manifold's local point, so after the sub-step's integration they are a sub-step newer than
+ *            dist and n, which the narrow phase made before the solve (Bullet reports the positions of the narrow phase).
+ *            The directions are btPlaneSpace1 of n as the solver evaluates it.
+ *   forces   the accumulated impulse the manifold persists, divided (a correctly rounded quotient) by sim_time_step —
+ *            pybullet's normalForce is the applied impulse over the time step: normal, direction 1, direction 2.  They are
+ *            those of the last sub-step the step (or srl_step_simulation) ran.
+ *   last_only  = 1 keeps the rows whose a or b is the last placed body, slot nb - 1, in their relative order:
+ *            `Simulator.contact_points`.
+ *   count    count_dev[e] is always the true total of the rows the call selects (all, or the last body's), whatever the
+ *            capacity; only the first `capacity` of them are written, to bodies_dev [n][capacity][2] and rows_dev
+ *            [n][capacity][20]; rows at or beyond min(count, capacity) are left untouched.
+ *   wrench   optional, wrench_dev [n][episode_length][8] per body slot: net contact force xyz, number of its points, net
+ *            contact torque about the body's position xyz, 0 (zeros for a slot >= nb).  Summed from zero over the body's rows
+ *            in the order above, each sum one addition per component: a row gives its A the force F = fma(t2, f2, fma(t1, f1,
+ *            n * fn)) per component and its B the force -F; the torque is cross(r, F) with r = the body's contact position
+ *            less its position.  One lane per body, no atomics: a loop in that order gives the same bits.  It always covers
+ *            all of the env's contacts, whatever capacity and last_only say.
+ * Enqueued on `stream` like a step: it sees the steps before it there, does not synchronise, reads the env and writes only
+ * the outputs (no header field, blob word or flag changes).  bodies_dev must be 8-byte aligned, rows_dev and wrench_dev
+ * 16-byte.  Refused with SRL_EINVAL: a null env, a null count, bodies or rows pointer, capacity < 1, last_only outside
+ * {0, 1}; with SRL_ENOMESH before srl_load_meshes. */
+int32_t srl_contact_row_words(void);
+/* The most points an env can hold: 4 * episode_length + 4 * manifold slots. */
+int srl_contact_max_points(srl_env* env, int32_t* max_points);
+int srl_contact_points(srl_env* env, int32_t last_only, int32_t capacity, int32_t* count_dev, int32_t* bodies_dev, float* rows_dev,
+                       float* wrench_dev /* may be null */, void* stream);
+
 /* Per-kernel HIP-event timing (bench.py's roofline leg).  enable != 0 brackets every kernel launch of
  * srl_reset/srl_step with events on the launch stream; srl_get_kernel_times synchronises and returns the
  * accumulated milliseconds and launch counts since the last call: index 0 = settle (K1+K4),

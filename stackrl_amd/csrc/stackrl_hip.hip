@@ -11,6 +11,7 @@
 #include "view.hip"
 #include "camera.hip"
 #include "state.hip"
+#include "contacts.hip"
 #include "env_host.h"   // fail / g_err, derive, layout, step_variant_of, state_layout, MeshTable: no HIP calls
 
 namespace {
@@ -68,8 +69,10 @@ struct srl_env {
   bool profiling = false;
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> pool;
-  float acc_ms[4] = {0, 0, 0, 0};   // 0 settle, 1 render, 2 srl_k_stage (hook / stale records only), 3 the two launch-order kernels
-  int acc_n[4] = {0, 0, 0, 0};
+  // 0 settle, 1 render, 2 srl_k_stage (hook / stale records only), 3 the two launch-order kernels, 4 srl_k_contact_points (kept
+  // out of the step's three; no export reports it)
+  float acc_ms[5] = {0, 0, 0, 0, 0};
+  int acc_n[5] = {0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -721,6 +724,40 @@ int srl_state_set_rng(srl_env* env, uint32_t seed, uint32_t sample_counter) {
     env->P.seed = seed;
     env->P_dirty = true;
   }
+  return SRL_OK;
+}
+
+// ---- contact points (contacts.hip)
+
+int32_t srl_contact_row_words(void) { return SRL_CONTACT_ROW_WORDS; }
+
+int srl_contact_max_points(srl_env* env, int32_t* max_points) {
+  if (!env) return fail(SRL_EINVAL, "srl_contact_max_points: null env");
+  if (!max_points) return fail(SRL_EINVAL, "srl_contact_max_points: null output");
+  *max_points = SRL_GMAXP * env->P.c.episode_length + 4 * env->P.NS;   // every ground manifold and every slot full
+  return SRL_OK;
+}
+
+int srl_contact_points(srl_env* env, int32_t last_only, int32_t capacity, int32_t* count_dev, int32_t* bodies_dev, float* rows_dev,
+                       float* wrench_dev, void* stream) {
+  if (!env) return fail(SRL_EINVAL, "srl_contact_points: null env");
+  if (capacity < 1) return fail(SRL_EINVAL, "srl_contact_points: capacity must be at least 1");   // (first: buffers of no rows are null)
+  if (last_only != 0 && last_only != 1) return fail(SRL_EINVAL, "srl_contact_points: last_only must be 0 or 1");
+  if (!count_dev || !bodies_dev || !rows_dev) return fail(SRL_EINVAL, "srl_contact_points: null output (count, bodies and rows are required)");
+  if (((uintptr_t)bodies_dev & 7) || ((uintptr_t)rows_dev & 15) || ((uintptr_t)wrench_dev & 15))
+    return fail(SRL_EINVAL, "srl_contact_points: bodies must be 8-byte aligned, rows and wrench 16-byte aligned");
+  if (!env->d_mh.get()) return fail(SRL_ENOMESH, "srl_contact_points: srl_load_meshes must be called first");
+  const DevParams& P = env->P;
+  static_assert(SRL_NSLOT_MAX >= 128, "the kernel's slot table holds every slot of nslots()");
+  ContactParams C;
+  C.hdr = P.hdr; C.blob = P.blob; C.mh = P.mh; C.mv = P.mv;
+  C.BLOB = P.BLOB; C.OFF_X = P.OFF_X; C.OFF_Q = P.OFF_Q; C.OFF_MESH = P.OFF_MESH; C.OFF_GM = P.OFF_GM; C.OFF_MAN = P.OFF_MAN;
+  C.OFF_POS = P.OFF_POS; C.NS = P.NS; C.NP = P.NP; C.L = P.c.episode_length; C.n_mesh = P.n_mesh;
+  C.dt = P.c.sim_time_step;
+  C.last_only = last_only; C.capacity = capacity;
+  C.count = count_dev; C.bodies = bodies_dev; C.rows = rows_dev; C.wrench = wrench_dev;
+  SRL_LAUNCH(env, 4, srl_k_contact_points, dim3(P.c.n_envs), dim3(SRL_CONTACT_THREADS), 0, (hipStream_t)stream, C);
+  HIP_TRY(hipGetLastError());
   return SRL_OK;
 }
 

@@ -433,6 +433,36 @@ class VecStackEnv(object):
     _check(self._lib.srl_get_contacts(self._h, _np_ptr(mp), _np_ptr(npts)))
     return mp, npts
 
+  def contact_max_points(self):
+    """`srl_contact_max_points`: the most contacts an env can hold (every ground manifold and every manifold slot full)."""
+    n = ctypes.c_int32()
+    _check(self._lib.srl_contact_max_points(self._h, ctypes.byref(n)))
+    return int(n.value)
+
+  def contact_points(self, last=False, capacity=None, wrench=False, out=None):
+    """The contact points of every env's pile after the latest step, gathered on the device (`srl_contact_points`;
+    include/stackrl_hip.h holds the definition): a `stackrl_amd.contacts.ContactPoints` of device tensors.
+      last      only the contacts of the last placed rock: the reference's `Simulator.contact_points` (simulator.py:131-133)
+      capacity  rows per env; None = `contact_max_points()`, which no env exceeds.  `count` is the true number either way
+      wrench    also the net contact force and torque on every body, [B, episode_length, 8]; it covers all contacts
+      out       a `ContactPoints` to fill in place of new tensors (its row count is the capacity); rows at or beyond an env's
+                count are left as they were
+    Runs on the env's stream like `render`: nothing is waited for, the env is only read."""
+    from stackrl_amd import contacts as _contacts
+    L = self.config.episode_length
+    if out is None:
+      C = self.contact_max_points() if capacity is None else int(capacity)
+      out = _contacts.empty(self._B, max(C, 0), L, wrench, self._device)   # (a capacity < 1: the export refuses, in its own words)
+    else:
+      C = _contacts.check_out(out, self._B, L, wrench, self._device)
+      if capacity is not None and int(capacity) != C:
+        raise ValueError('capacity {} is not the row count of out ({})'.format(capacity, C))
+    w = out.wrench if wrench else None
+    self._launch('srl_contact_points', int(last), C, out.count.data_ptr(),
+                 out.bodies.data_ptr(), out.rows.data_ptr(), None if w is None else w.data_ptr(),
+                 tensors=(out.count, out.bodies, out.rows, w))
+    return out if wrench or out.wrench is None else _contacts.ContactPoints(out.count, out.bodies, out.rows, None)
+
   def maps(self):
     Hm = np.zeros((self._B, self._H, self._H), np.float32)
     Om = np.zeros((self._B, self._hh, self._hh) if self._no == 1 else (self._B, self._no, self._hh, self._hh), np.float32)
@@ -695,6 +725,20 @@ class PipelinedVecStackEnv(object):
       e.render_camera(width, height, camera, rgb, depth, ids, out=[t[sl] for t in full],
                       scene=None if scene is None else tuple(a[sl] for a in scene))
     return full[0] if len(full) == 1 else tuple(full)
+
+  def contact_points(self, last=False, capacity=None, wrench=False):
+    """`VecStackEnv.contact_points` of the whole batch, in env order: every group writes its slice, after its own latest step."""
+    from stackrl_amd import contacts as _contacts
+    e0 = self._envs[0]
+    C = e0.contact_max_points() if capacity is None else int(capacity)
+    if C < 1:                                     # the first group's call raises, in the export's words
+      return e0.contact_points(last, C, wrench)
+    full = _contacts.empty(self._B, C, self.config.episode_length, wrench, self._device)
+    for k, e in enumerate(self._envs):
+      sl = self._slice(k)
+      e.contact_points(last, None, wrench, out=_contacts.ContactPoints(full.count[sl], full.bodies[sl], full.rows[sl],
+                                                                       full.wrench[sl] if wrench else None))
+    return full
 
   def state_signature(self):
     return self._envs[0].state_signature()

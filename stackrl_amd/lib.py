@@ -45,6 +45,9 @@ _SIGS = {
   'srl_state_get': (ctypes.c_int, [_VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP]),
   'srl_state_set': (ctypes.c_int, [_VP, ctypes.c_uint64, _VP, _VP, ctypes.c_int32, _VP, _VP]),
   'srl_state_set_rng': (ctypes.c_int, [_VP, ctypes.c_uint32, ctypes.c_uint32]),
+  'srl_contact_row_words': (ctypes.c_int32, []),
+  'srl_contact_max_points': (ctypes.c_int, [_VP, _VP]),
+  'srl_contact_points': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(sorted(_SIGS))
 
