@@ -199,7 +199,7 @@ int srl_state_signature(srl_env* env, uint64_t* signature);
 /* Gathers the records of the envs idx_dev[0 .. n) (int32, device; NULL = all n = n_envs envs in order) into records_dev
  * [n][words] and returns the handle's seed and sample counter (host pointers, either may be NULL).  Enqueued on `stream`
  * like srl_step: no blocking copy, no allocation.  Refused with SRL_EINVAL while the staged records are stale: after
- * srl_load_meshes, srl_set_body_state or srl_step_simulation and before the next step. */
+ * srl_load_meshes, srl_set_body_state, srl_kick or srl_step_simulation and before the next step. */
 int srl_state_get(srl_env* env, const int32_t* idx_dev, int32_t n, void* records_dev, uint32_t* seed, uint32_t* sample_counter,
                   void* stream);
 /* Env dst_idx_dev[i] takes record src_rec_dev[i] of records_dev, i < n (int32, device; NULL = i).  Records may repeat (a
@@ -261,6 +261,49 @@ int32_t srl_contact_row_words(void);
 int srl_contact_max_points(srl_env* env, int32_t* max_points);
 int srl_contact_points(srl_env* env, int32_t last_only, int32_t capacity, int32_t* count_dev, int32_t* bodies_dev, float* rows_dev,
                        float* wrench_dev /* may be null */, void* stream);
+
+/* ---- Push test: does the pile stand?  Fork it (the state records above), give its bodies a velocity increment, let it move
+ * (srl_step_simulation), measure how far every body went — with no copy to the host (csrc/push.hip).  Three hooks: the poses
+ * of every env (`Simulator.poses` / `positions`, simulator.py:85-93), the increment, and the distances
+ * (`Simulator.distances`, simulator.py:95-111, and `distances_from_place`, :113-128).  In all three L = episode_length,
+ * n = n_envs, nb = the env's number of placed bodies kept inside [0, L]; pose and velocity rows have the columns of
+ * srl_get_state / srl_get_velocities with L slots per env in place of SRL_MAX_BODIES; every pointer is device memory, 16-byte
+ * aligned (the body counts: 4); the call is enqueued on `stream` like a step, with no blocking copy and no allocation.
+ * Float32 with one rounding per written operation; dot(a, b) = fma(a.x, b.x, fma(a.y, b.y, a.z * b.z)).
+ *   poses      poses_dev [n][L][8]: x y z qx qy qz qw and the mesh id as the bit pattern of an int32, for the slots below nb;
+ *              zero rows for the others.  n_bodies_dev [n] = nb.  The env is only read.
+ *   kick       adds an increment to the velocities of the selected bodies, one float32 addition per component: the linear
+ *              velocity takes columns 0 - 2 of the body's row of dv_dev, the angular one columns 4 - 6 (columns 3 and 7 are
+ *              not read into anything).  per_body = 1: dv_dev is [n][L][8], a row per body slot; per_body = 0: dv_dev is
+ *              [n][8], one row per env for every selected body.  select = SRL_KICK_ALL: every slot below nb; SRL_KICK_LAST:
+ *              slot nb - 1, the last placed body; 0 .. L - 1: that slot where it is below nb.  A slot at or above nb is never
+ *              written, so an env with nb = 0 is not touched.  Like srl_set_body_state it leaves the staged records stale:
+ *              srl_state_get is refused until the next step.
+ *   distances  per body slot b below nb a row of 4 words, rows_dev [n][L][4]: perr oerr dz speed (zeros for the others).  Its
+ *              reference pose (p, a) is row b of ref_dev [n][L][8] — but the body's place pose, the one the reward's discount
+ *              measures from, when ref_dev is NULL or b >= ref_nb_dev[e] (ref_nb_dev NULL: every row of ref_dev counts).  So
+ *              with ref_dev = NULL the rows are `distances_from_place`, and with the poses and counts srl_poses gave before
+ *              a step they are `Simulator.distances` of that step: a body new in it starts from its place pose
+ *              (simulator.py:227-237).  With x, q the body's pose and v, w its velocities:
+ *                perr  = sqrt(dot(d, d)), d = p - x per component
+ *                oerr  = 2 acos(min(|(a0 q0 + a1 q1) + (a2 q2 + a3 q3)|, 1)), acos the library's own polynomial: what the
+ *                        discounted metrics compute (rewarder.py:261-269)
+ *                dz    = x.z - p.z
+ *                speed = sqrt(dot(v, v))
+ *   summary    summary_dev [n][8] per env: nb, moved, max perr, max oerr, the sum of perr, min dz, max speed, max
+ *              sqrt(dot(w, w)) — all float32.  moved counts the bodies for which NOT (perr <= tol_p AND oerr <= tol_o), so a
+ *              NaN counts as moved.  Every word is made by a loop over b = 0 .. nb - 1 in this order starting from 0: the
+ *              maxima by fmax, the minimum by fmin (a NaN operand is passed over), the sum with one rounding per addition.
+ *              No atomics: a loop in that order gives the same bits.
+ * srl_poses and srl_pose_distances read the env and write only their outputs.  Refused with SRL_EINVAL before any launch: a
+ * null env, a null output or increment pointer, a pointer off its alignment, per_body outside {0, 1}, select below
+ * SRL_KICK_LAST or at or above L. */
+#define SRL_KICK_ALL (-1)
+#define SRL_KICK_LAST (-2)
+int srl_poses(srl_env* env, float* poses_dev, int32_t* n_bodies_dev, void* stream);
+int srl_kick(srl_env* env, const float* dv_dev, int32_t per_body, int32_t select, void* stream);
+int srl_pose_distances(srl_env* env, const float* ref_dev /* may be null */, const int32_t* ref_nb_dev /* may be null */, float tol_p,
+                       float tol_o, float* rows_dev, float* summary_dev, void* stream);
 
 /* Per-kernel HIP-event timing (bench.py's roofline leg).  enable != 0 brackets every kernel launch of
  * srl_reset/srl_step with events on the launch stream; srl_get_kernel_times synchronises and returns the

@@ -12,6 +12,7 @@
 #include "camera.hip"
 #include "state.hip"
 #include "contacts.hip"
+#include "push.hip"
 #include "env_host.h"   // fail / g_err, derive, layout, step_variant_of, state_layout, MeshTable: no HIP calls
 
 namespace {
@@ -69,8 +70,8 @@ struct srl_env {
   bool profiling = false;
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> pool;
-  // 0 settle, 1 render, 2 srl_k_stage (hook / stale records only), 3 the two launch-order kernels, 4 srl_k_contact_points (kept
-  // out of the step's three; no export reports it)
+  // 0 settle, 1 render, 2 srl_k_stage (hook / stale records only), 3 the two launch-order kernels, 4 srl_k_contact_points and the
+  // three kernels of push.hip (kept out of the step's three; no export reports it)
   float acc_ms[5] = {0, 0, 0, 0, 0};
   int acc_n[5] = {0, 0, 0, 0, 0};
 };
@@ -683,7 +684,7 @@ int srl_state_get(srl_env* env, const int32_t* idx_dev, int32_t n, void* records
   if (!env->d_mh.get()) return fail(SRL_ENOMESH, "srl_load_meshes must be called first");
   if (!idx_dev && n != env->P.c.n_envs) return fail(SRL_EINVAL, "srl_state_get: without indexes n must be the handle's n_envs");
   if (env->stage_dirty)
-    return fail(SRL_EINVAL, "srl_state_get: the staged records are stale (no step since srl_load_meshes, srl_set_body_state or srl_step_simulation): step first");
+    return fail(SRL_EINVAL, "srl_state_get: the staged records are stale (no step since srl_load_meshes, srl_set_body_state, srl_kick or srl_step_simulation): step first");
   StateParts S; dim3 grid;
   state_launch_shape(env, n, S, grid);
   hipLaunchKernelGGL(srl_k_state_get, grid, dim3(SRL_STATE_THREADS), 0, (hipStream_t)stream, S, idx_dev, (int)n, (uint4*)records_dev);
@@ -757,6 +758,53 @@ int srl_contact_points(srl_env* env, int32_t last_only, int32_t capacity, int32_
   C.last_only = last_only; C.capacity = capacity;
   C.count = count_dev; C.bodies = bodies_dev; C.rows = rows_dev; C.wrench = wrench_dev;
   SRL_LAUNCH(env, 4, srl_k_contact_points, dim3(P.c.n_envs), dim3(SRL_CONTACT_THREADS), 0, (hipStream_t)stream, C);
+  HIP_TRY(hipGetLastError());
+  return SRL_OK;
+}
+
+// ---- push test (push.hip)
+
+static PushParams push_params(const srl_env* env) {
+  const DevParams& P = env->P;
+  PushParams C;
+  C.hdr = P.hdr; C.blob = P.blob;
+  C.BLOB = P.BLOB; C.OFF_X = P.OFF_X; C.OFF_Q = P.OFF_Q; C.OFF_V = P.OFF_V; C.OFF_PX = P.OFF_PX; C.OFF_PQ = P.OFF_PQ;
+  C.OFF_MESH = P.OFF_MESH; C.L = P.c.episode_length;
+  return C;
+}
+
+int srl_poses(srl_env* env, float* poses_dev, int32_t* n_bodies_dev, void* stream) {
+  if (!env) return fail(SRL_EINVAL, "srl_poses: null env");
+  if (!poses_dev || !n_bodies_dev) return fail(SRL_EINVAL, "srl_poses: null output (poses and n_bodies are required)");
+  if ((uintptr_t)poses_dev & 15) return fail(SRL_EINVAL, "srl_poses: poses must be 16-byte aligned");
+  SRL_LAUNCH(env, 4, srl_k_poses, dim3(env->P.c.n_envs), dim3(SRL_PUSH_THREADS), 0, (hipStream_t)stream, push_params(env), poses_dev,
+             n_bodies_dev);
+  HIP_TRY(hipGetLastError());
+  return SRL_OK;
+}
+
+int srl_kick(srl_env* env, const float* dv_dev, int32_t per_body, int32_t select, void* stream) {
+  if (!env) return fail(SRL_EINVAL, "srl_kick: null env");
+  if (!dv_dev) return fail(SRL_EINVAL, "srl_kick: null increments");
+  if ((uintptr_t)dv_dev & 15) return fail(SRL_EINVAL, "srl_kick: the increments must be 16-byte aligned");
+  if (per_body != 0 && per_body != 1) return fail(SRL_EINVAL, "srl_kick: per_body must be 0 or 1");
+  if (select < SRL_KICK_LAST || select >= env->P.c.episode_length)
+    return fail(SRL_EINVAL, "srl_kick: select must be SRL_KICK_ALL, SRL_KICK_LAST or a body slot below episode_length");
+  SRL_LAUNCH(env, 4, srl_k_kick, dim3(env->P.c.n_envs), dim3(SRL_PUSH_THREADS), 0, (hipStream_t)stream, push_params(env), dv_dev,
+             (int)per_body, (int)select);
+  HIP_TRY(hipGetLastError());
+  env->stage_dirty = true;   // as after srl_set_body_state: bodies change behind the staged records' back
+  return SRL_OK;
+}
+
+int srl_pose_distances(srl_env* env, const float* ref_dev, const int32_t* ref_nb_dev, float tol_p, float tol_o, float* rows_dev,
+                       float* summary_dev, void* stream) {
+  if (!env) return fail(SRL_EINVAL, "srl_pose_distances: null env");
+  if (!rows_dev || !summary_dev) return fail(SRL_EINVAL, "srl_pose_distances: null output (rows and summary are required)");
+  if (((uintptr_t)ref_dev & 15) || ((uintptr_t)rows_dev & 15) || ((uintptr_t)summary_dev & 15))
+    return fail(SRL_EINVAL, "srl_pose_distances: the reference, rows and summary must be 16-byte aligned");
+  SRL_LAUNCH(env, 4, srl_k_pose_distances, dim3(env->P.c.n_envs), dim3(SRL_PUSH_THREADS), 0, (hipStream_t)stream, push_params(env), ref_dev,
+             ref_nb_dev, tol_p, tol_o, rows_dev, summary_dev);
   HIP_TRY(hipGetLastError());
   return SRL_OK;
 }

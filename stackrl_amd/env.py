@@ -463,6 +463,65 @@ class VecStackEnv(object):
                  tensors=(out.count, out.bodies, out.rows, w))
     return out if wrench or out.wrench is None else _contacts.ContactPoints(out.count, out.bodies, out.rows, None)
 
+  # ---- push test (stackrl_amd/push.py; csrc/push.hip)
+  def poses(self, out=None):
+    """`Simulator.poses` of every env on the device (`srl_poses`): (poses float32 [B, L, 8], n_bodies int32 [B]) with L =
+    episode_length — per body slot x y z qx qy qz qw and the mesh id as the bits of an int32 (`poses[..., 7].view(torch.int32)`),
+    zero rows at or above the env's body count.  out: (poses, n_bodies) tensors to fill.  Runs on the env's stream like
+    `render`: nothing is waited for, the env is only read."""
+    from stackrl_amd import push as _push
+    L = self.config.episode_length
+    if out is None:
+      out = (torch.empty((self._B, L, 8), dtype=torch.float32, device=self._device), torch.empty(self._B, dtype=torch.int32, device=self._device))
+    poses, nb = out
+    _push.check_tensors('out', [(poses, (self._B, L, 8), torch.float32), (nb, (self._B,), torch.int32)], self._device)
+    self._launch('srl_poses', poses.data_ptr(), nb.data_ptr(), tensors=(poses, nb))
+    return poses, nb
+
+  def kick(self, dv, select='all'):
+    """Adds the velocity increment `dv` to the placed rocks on the device (`srl_kick`): [B, 8] or [B, 3], one increment per
+    env, or [B, L, 8] or [B, L, 3], one per body slot; columns 0 - 2 are linear (m/s), 4 - 6 angular (rad/s), the 3-column forms
+    linear only.  select: 'all' rocks, the 'last' placed one, or a body slot (a slot the env has not filled is left alone).
+    Nothing is waited for.  Like `set_body_state` it leaves the staged records stale: `get_state` is refused until the next
+    step."""
+    from stackrl_amd import push as _push
+    self._require_reset('kick')
+    dv, per_body = _push.increments(dv, self._B, self.config.episode_length, self._device)
+    self._launch('srl_kick', dv.data_ptr(), per_body, _push.select_code(select), tensors=(dv,))
+
+  def distances(self, since=None, tol=None, out=None):
+    """How far every rock is from a reference pose, measured on the device (`srl_pose_distances`): a
+    `stackrl_amd.push.PoseDistances`.  since=None measures from the pose each rock was placed at — the reference's
+    `Simulator.distances_from_place`, what the discounted rewards use; since=(poses, n_bodies) as `poses()` returned them
+    earlier measures from there (a rock placed since: from its place pose; n_bodies None: every row counts) — `Simulator.distances`
+    of the steps between.
+    tol = (metres, radians) beyond which a rock counts as `moved` (None: `push.default_tol`).  out: a `PoseDistances` to
+    fill.  Nothing is waited for, the env is only read."""
+    from stackrl_amd import push as _push
+    L = self.config.episode_length
+    tp, to = _push.default_tol(self.config) if tol is None else tol
+    if out is None:
+      out = _push.empty(self._B, L, self._device, self.config.velocity_threshold)
+    _push.check_tensors('out', [(out.rows, (self._B, L, _push.ROW_WORDS), torch.float32),
+                                (out.summary, (self._B, _push.SUMMARY_WORDS), torch.float32)], self._device)
+    ref, ref_nb = (None, None) if since is None else since
+    if since is not None:      # (n_bodies may be None: every row of the poses counts)
+      _push.check_tensors('since', [(ref, (self._B, L, 8), torch.float32)] + ([] if ref_nb is None else [(ref_nb, (self._B,), torch.int32)]),
+                          self._device)
+    self._launch('srl_pose_distances', None if ref is None else ref.data_ptr(), None if ref_nb is None else ref_nb.data_ptr(),
+                 float(tp), float(to), out.rows.data_ptr(), out.summary.data_ptr(), tensors=(ref, ref_nb, out.rows, out.summary))
+    return out
+
+  def push(self, dv, substeps, select='all', tol=None):
+    """A push test IN PLACE: `poses()`, `kick(dv, select)`, `step_simulation(substeps)`, then `distances(since=...)` from the
+    poses before the kick.  The env's own piles are pushed (use `push.PushTest` for a fork): until the next step the latest
+    observation no longer shows them and the staged records are stale, so `get_state` is refused; the next step renders the
+    piles as the push left them.  Waits for the sub-steps as `step_simulation` does."""
+    before = self.poses()
+    self.kick(dv, select)
+    self.step_simulation(substeps)
+    return self.distances(since=before, tol=tol)
+
   def maps(self):
     Hm = np.zeros((self._B, self._H, self._H), np.float32)
     Om = np.zeros((self._B, self._hh, self._hh) if self._no == 1 else (self._B, self._no, self._hh, self._hh), np.float32)
@@ -739,6 +798,41 @@ class PipelinedVecStackEnv(object):
       e.contact_points(last, None, wrench, out=_contacts.ContactPoints(full.count[sl], full.bodies[sl], full.rows[sl],
                                                                        full.wrench[sl] if wrench else None))
     return full
+
+  def poses(self):
+    """`VecStackEnv.poses` of the whole batch, in env order: every group writes its slice, after its own latest step."""
+    L = self.config.episode_length
+    poses = torch.empty((self._B, L, 8), dtype=torch.float32, device=self._device)
+    nb = torch.empty(self._B, dtype=torch.int32, device=self._device)
+    for k, e in enumerate(self._envs):
+      e.poses(out=(poses[self._slice(k)], nb[self._slice(k)]))
+    return poses, nb
+
+  def kick(self, dv, select='all'):
+    """`VecStackEnv.kick` over the groups, after `drain()`: `dv` holds the whole batch in env order."""
+    from stackrl_amd import push as _push
+    dv, _ = _push.increments(dv, self._B, self.config.episode_length, self._device)
+    self.drain()
+    for k, e in enumerate(self._envs):
+      e.kick(dv[self._slice(k)], select)
+
+  def distances(self, since=None, tol=None):
+    """`VecStackEnv.distances` of the whole batch, in env order: every group writes its slice, after its own latest step."""
+    from stackrl_amd import push as _push
+    full = _push.empty(self._B, self.config.episode_length, self._device, self.config.velocity_threshold)
+    for k, e in enumerate(self._envs):
+      sl = self._slice(k)
+      e.distances(since=None if since is None else (since[0][sl], since[1][sl]), tol=tol,
+                  out=_push.PoseDistances(full.rows[sl], full.summary[sl], full.velocity_threshold))
+    return full
+
+  def push(self, dv, substeps, select='all', tol=None):
+    """`VecStackEnv.push` of the whole batch, in place, after `drain()`."""
+    before = self.poses()
+    self.kick(dv, select)
+    for e in self._envs:
+      e.step_simulation(substeps)
+    return self.distances(since=before, tol=tol)
 
   def state_signature(self):
     return self._envs[0].state_signature()

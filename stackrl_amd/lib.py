@@ -48,6 +48,9 @@ _SIGS = {
   'srl_contact_row_words': (ctypes.c_int32, []),
   'srl_contact_max_points': (ctypes.c_int, [_VP, _VP]),
   'srl_contact_points': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP]),
+  'srl_poses': (ctypes.c_int, [_VP, _VP, _VP, _VP]),
+  'srl_kick': (ctypes.c_int, [_VP, _VP, ctypes.c_int32, ctypes.c_int32, _VP]),
+  'srl_pose_distances': (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_float, ctypes.c_float, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(sorted(_SIGS))
 

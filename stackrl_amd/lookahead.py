@@ -38,6 +38,12 @@ def choose(cand, reward):
   return cand.gather(1, best[:, None])[:, 0]
 
 
+def score(reward, distances, penalty):
+  """reward - penalty * moved / nb per candidate [B, k]: the simulated reward less the share of the pile's rocks that a push
+  moves beyond its tolerances (`PoseDistances.moved`, `nb`; an env without a body has none to move)."""
+  return reward - float(penalty) * (distances.moved / torch.clamp(distances.nb, min=1.0)).to(reward.device)
+
+
 class Lookahead(object):
   def __init__(self, env, k, **kwargs):
     """env: a `VecStackEnv` (or `PipelinedVecStackEnv` / `StartedVecStackEnv`) of B envs; k: actions evaluated per env.
@@ -70,20 +76,14 @@ class Lookahead(object):
       if sig != self.signature:
         raise ValueError('the scratch env does not share the env\'s state signature')
 
-  def evaluate(self, actions, observations=False):
-    """actions int64 [B, k] -> (reward [B, k(, keys)], done [B, k]) of one step with each, plus with `observations`
-    (obs_map [B, k, H, W, 2], obs_obj [B, k, ...]) in front.  `ValueError` at the auto-reset point (no rock left): there
-    the step draws the next episode from the slot's stream."""
+  def fork(self):
+    """Every scratch env takes its env's state record, k forks of each (csrc/state.hip); `env` is only read.  Returns the rocks
+    the episode has left."""
     env = self.env
     first = env._envs[0] if hasattr(env, '_envs') else env
     first._require_reset('Lookahead.evaluate')
     self._follow_pool()
     left = first._left
-    if left == 0:
-      raise ValueError('Lookahead.evaluate at the auto-reset point: the next step resets the envs and its result depends on the slot')
-    actions = torch.as_tensor(actions).to(device=self.scratch._device, dtype=torch.int64)
-    if tuple(actions.shape) != (self.B, self.k):
-      raise ValueError('actions must have shape [{}, {}]'.format(self.B, self.k))
     if hasattr(env, '_envs'):
       env.drain()
       records = torch.cat([e._get_records()[0] for e in env._envs])
@@ -93,11 +93,33 @@ class Lookahead(object):
     s._set_records(records, env.state_signature(), None, self._source)   # (the export refuses records of another signature)
     s._left = left
     s._needs_reset = False      # every scratch env now holds a record of the table the scratch has
+    return left
+
+  def evaluate(self, actions, observations=False, push=None):
+    """actions int64 [B, k] -> (reward [B, k(, keys)], done [B, k]) of one step with each, plus with `observations`
+    (obs_map [B, k, H, W, 2], obs_obj [B, k, ...]) in front.  `ValueError` at the auto-reset point (no rock left): there
+    the step draws the next episode from the slot's stream.
+    With `push`, a `stackrl_amd.push.PushSpec`, every stepped fork is then pushed in place (its state is disposable) and the
+    `PoseDistances` [B, k, ...] of the push follow the reward and done: how far the pile with the new rock on it moves."""
+    env = self.env
+    first = env._envs[0] if hasattr(env, '_envs') else env
+    first._require_reset('Lookahead.evaluate')
+    if first._left == 0:
+      raise ValueError('Lookahead.evaluate at the auto-reset point: the next step resets the envs and its result depends on the slot')
+    actions = torch.as_tensor(actions).to(device=self.scratch._device, dtype=torch.int64)
+    if tuple(actions.shape) != (self.B, self.k):
+      raise ValueError('actions must have shape [{}, {}]'.format(self.B, self.k))
+    self.fork()
+    s = self.scratch
     (om, oo), r, d = s.step(actions.reshape(-1), block=True)
     shape = (self.B, self.k)
     out = (r.reshape(shape + tuple(r.shape[1:])), d.reshape(shape))
     if observations:
       out = ((om.reshape(shape + tuple(om.shape[1:])), oo.reshape(shape + tuple(oo.shape[1:]))),) + out
+    if push is not None:
+      dv = push.draw(self.B, self.k, s.config.episode_length, s._device)
+      moved = s.push(dv.reshape((self.B * self.k,) + tuple(dv.shape[2:])), push.substeps, select=push.select, tol=push.tol)
+      out = out + (moved.reshape(*shape),)
     return out
 
 
@@ -110,11 +132,17 @@ class LookaheadPolicy(object):
   With an integer `radius` the candidates are spread (stackrl_amd/candidates.py, include/stackrl_candidates.h): every
   candidate strikes the entries of its map within `radius` pixels, and the next one is the best entry left; `last_count` [B]
   then says how many distinct candidates an env had (the slots beyond repeat candidate 0).  Radius 0 gives the candidates of
-  `radius=None`, picked by the kernel; k is at most 32 there."""
+  `radius=None`, picked by the kernel; k is at most 32 there.
 
-  def __init__(self, base, lookahead, radius=None):
+  With `push`, a `stackrl_amd.push.PushSpec`, every candidate's pile is pushed after its step (`Lookahead.evaluate(push=...)`)
+  and a candidate's score is `reward - penalty * moved / nb` (`score`): the share of the pile's rocks the push moves beyond the
+  spec's tolerances costs `penalty`.  The tie rule is the same; `last_push` holds the latest `PoseDistances`.  With
+  `push=None` nothing changes."""
+
+  def __init__(self, base, lookahead, radius=None, push=None, penalty=0.0):
     self.base, self.lookahead = base, lookahead
     self.radius = None if radius is None else int(radius)
+    self.push, self.penalty = push, float(penalty)
     self.last_count = None
     if self.radius is not None:
       from stackrl_amd import candidates as _candidates
@@ -141,8 +169,13 @@ class LookaheadPolicy(object):
     cand, values = self.candidates(obs, n_valid)
     if cand.shape[1] == 1:
       return cand[:, 0], values
-    reward = self.lookahead.evaluate(cand)[0]
+    if self.push is None:
+      reward = self.lookahead.evaluate(cand)[0]
+    else:
+      reward, _, self.last_push = self.lookahead.evaluate(cand, push=self.push)
     if reward.dim() != 2:
       raise ValueError('LookaheadPolicy needs one reward per env and action, got {}'.format(tuple(reward.shape)))
     self.last = (cand, reward)
+    if self.push is not None:
+      reward = score(reward, self.last_push, self.penalty)
     return choose(cand, reward.to(cand.device)), values
